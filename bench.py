@@ -16,29 +16,42 @@ Workloads (--workload):
   c5            one step = zfp_compress in reversible (lossless) mode of one
                 512x512x512x64 float32 w-slab of the 512^4 field of configs[4]
                 (4D blocks); rank r owns slab r (8 ranks = the whole field).
-                The lossless round trip is checked on the device.
+                With --full the lossless round trip is checked on the device.
 Chunks are independent zfp streams, so the timed region has no collective; the
 RCCL gather that concatenates the chunk streams on rank 0 is timed separately
-and reported as `gather`, never inside `value`.
+and reported as `gather` (--full), never inside `value`.
 
 --gpus N without WORLD_SIZE in the environment re-launches this script under
 torch.distributed.run with N ranks (before anything touches a GPU) and exits
 with its status.  --dry-run runs the launcher, barriers and max-over-ranks
 timing on CPU with gloo (a numpy copy stands in for the codec) -- for tests.
 
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs
+and prints the result line; the legs that take runs of their own come with --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+returned to its caller (rank 0): stream_nbytes.npy, the size zfp_compress
+returned (float64), and stream.npy, the stream's bytes as float32 0..255 -- all
+of a stream of at most 2^23 bytes, else the bytes at 2^23 sorted offsets drawn
+from a fixed seed (stream_sample_offsets).  The field is a function of the
+arguments alone, so two builds run with the same arguments compare output for
+output.
+
 Printed JSON (rank 0): the contract keys plus
   roofline      dominant kernel (c2: encode3_aligned_full) against HBM peak: achieved =
                 algorithmic bytes per launch (4 B read + R/8 B written per value)
-                / mean kernel time from HIP events on the kernel's own stream;
-                traffic = PMC HBM bytes per encode call (every dispatch of the call summed)
-                from profiles/<round>_pmc_<workload>.json made by tools/pmc_bench.sh for
-                the same workload and field (gfx950 FETCH_SIZE x2 correction), else null
-                with traffic_null_reason
-  cpu_baseline  the reference itself (oracle/_ref/libzfp_ref.so, compiled from
-                /root/reference), OpenMP, every core this process may use, on
-                the full per-GPU field (c2)
+                / mean kernel time of the timed steps, from HIP events on the kernel's
+                own stream; traffic = PMC HBM bytes per encode call (every dispatch of
+                the call summed) from profiles/<round>_pmc_<workload>.json made by
+                tools/pmc_bench.sh for the same workload and field (gfx950 FETCH_SIZE x2
+                correction), else null with traffic_null_reason
+and with --full
+  cpu_baseline  the reference itself (oracle/_ref/libzfp_ref.so, the reference pin
+                built by `make -C oracle ref`), OpenMP, every core this process may
+                use, on the full per-GPU field (c2)
   decode_*      zfp_decompress of the same stream (same field, device-resident)
   bitexact      GPU stream bytes == reference CPU stream bytes (whole field)
+  gather        the RCCL gather of the chunk streams (--gpus N > 1)
 """
 import argparse
 import ctypes
@@ -77,7 +90,44 @@ def parse_args(argv=None):
                     help="smooth: F1 (SURVEY 8d, the metric's field); rough: F2, uniform [-1, 1) -- every bit "
                          "plane dense, the coder's worst load")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo plumbing check, no GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: decode of the same "
+                         "stream and its round-trip check, the RCCL gather, the CPU baseline and the bit-exact "
+                         "comparison with the reference (--no-cpu skips the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (rank 0)")
     return ap.parse_args(argv)
+
+
+DUMP_STREAM_BYTES = 1 << 23  # stream.npy holds at most this many stream bytes, one float32 each (32 MiB)
+DUMP_SEED = 20240611
+
+
+def dump_arrays(dirname, arrays):
+    """DIR/<name>.npy for each array, float32 or float64 as given."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def stream_sample_offsets(nbytes):
+    """Byte offsets of the stream that stream.npy holds: all of a short stream, else a fixed sorted
+    sample drawn once from numpy default_rng(DUMP_SEED) -- the same offsets for the same stream length."""
+    if nbytes <= DUMP_STREAM_BYTES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, nbytes, size=DUMP_STREAM_BYTES, dtype=np.int64))
+
+
+def dump_stream(torch, dirname, out_t, nbytes):
+    """What a caller of the timed zfp_compress receives: the byte count it returned and the stream
+    it left in the device buffer.  stream.npy: the stream's bytes (or the sample of
+    stream_sample_offsets) as float32 0..255; stream_nbytes.npy: the returned size, float64."""
+    nbytes = int(nbytes)
+    off = stream_sample_offsets(nbytes)
+    got = out_t[:nbytes] if off is None else out_t[torch.from_numpy(off).to(out_t.device)]
+    dump_arrays(dirname, {"stream": got.cpu().numpy().astype(np.float32),
+                          "stream_nbytes": np.array([nbytes], dtype=np.float64)})
 
 
 def relaunch(args):
@@ -391,39 +441,48 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         ms = float(tt.item())
 
-    # decode of the same stream into a device buffer (reported, not the metric); variable-rate
-    # streams decode with the block index the compress call left on the stream
-    back_t = torch.empty_like(field_t)
-    lib.zfp_field_set_pointer(zf, ctypes.c_void_p(back_t.data_ptr()))
-    dms, dkms = [], []
-    n_decode = max(3, args.steps // 2)
-    for i in range(n_decode):
-        lib.zfp_stream_rewind(zs)
-        if hdr_field is not None:
-            lib.stream_rseek(bs, 96)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        if lib.zfp_decompress(zs, zf) == 0:
-            raise RuntimeError("zfp_decompress failed: %s" % lib.zfp_hip_last_error())
-        torch.cuda.synchronize()
-        if i:
-            dms.append((time.perf_counter() - t1) * 1e3)
-            k, t = ctypes.c_double(), ctypes.c_double()
-            lib.zfp_hip_last_timing(ctypes.byref(k), ctypes.byref(t))
-            dkms.append(k.value)
-    lib.zfp_field_set_pointer(zf, ctypes.c_void_p(field_t.data_ptr()))
-    roundtrip = {}
-    if wl["mode"] == "reversible":
-        roundtrip["lossless_roundtrip"] = bool(torch.equal(back_t, field_t))
-    else:
-        roundtrip["decode_max_abs_err"] = float((back_t - field_t).abs().max().item())
-    del back_t
+    if args.dump_outputs and rank == 0:
+        dump_stream(torch, args.dump_outputs, out_t, nbytes)
+
+    # everything from here to the result line is --full only: a plain run has its figure already
+    extra, roundtrip = {}, {}
+    n_decode = 0
+    if args.full:
+        # decode of the same stream into a device buffer (reported, not the metric); variable-rate
+        # streams decode with the block index the compress call left on the stream
+        back_t = torch.empty_like(field_t)
+        lib.zfp_field_set_pointer(zf, ctypes.c_void_p(back_t.data_ptr()))
+        dms, dkms = [], []
+        n_decode = max(3, args.steps // 2)
+        for i in range(n_decode):
+            lib.zfp_stream_rewind(zs)
+            if hdr_field is not None:
+                lib.stream_rseek(bs, 96)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if lib.zfp_decompress(zs, zf) == 0:
+                raise RuntimeError("zfp_decompress failed: %s" % lib.zfp_hip_last_error())
+            torch.cuda.synchronize()
+            if i:
+                dms.append((time.perf_counter() - t1) * 1e3)
+                k, t = ctypes.c_double(), ctypes.c_double()
+                lib.zfp_hip_last_timing(ctypes.byref(k), ctypes.byref(t))
+                dkms.append(k.value)
+        lib.zfp_field_set_pointer(zf, ctypes.c_void_p(field_t.data_ptr()))
+        extra["decode_ms"] = round(float(np.mean(dms)), 4) if dms else None
+        extra["decode_kernel_ms"] = round(float(np.mean(dkms)), 4) if dkms else None
+        extra["decode_GBps"] = round(nvals * es / (np.mean(dms) * 1e-3) / 1e9, 2) if dms else None
+        if wl["mode"] == "reversible":
+            roundtrip["lossless_roundtrip"] = bool(torch.equal(back_t, field_t))
+        else:
+            roundtrip["decode_max_abs_err"] = float((back_t - field_t).abs().max().item())
+        del back_t
 
     # gather of the chunk streams to rank 0 over RCCL (timed separately): every rank
     # sends exactly its stream (point to point, no padding to the largest), as
     # zfpy.distributed.gather_streams does
     gather = None
-    if distributed:
+    if args.full and distributed:
         sizes = torch.zeros(world, device=dev, dtype=torch.int64)
         sizes[rank] = nbytes
         dist.all_reduce(sizes, op=dist.ReduceOp.SUM)
@@ -474,16 +533,15 @@ def main():
                          "traffic_per": "encode call (every dispatch of the call summed)",
                          **({"traffic_null_reason": treason} if traffic is None else {})},
             "call_ms": round(float(np.mean(tms)), 4),
-            "decode_ms": round(float(np.mean(dms)), 4) if dms else None,
-            "decode_kernel_ms": round(float(np.mean(dkms)), 4) if dkms else None,
-            "decode_GBps": round(nvals * es / (np.mean(dms) * 1e-3) / 1e9, 2) if dms else None,
-            "gather": gather,
+            **extra,
+            **({"gather": gather} if args.full else {}),
             "clock_warmup": {"ms": args.clock_warm_ms, "launches": warm_launches},
             "workload_key": args.workload,
             "calls": {"encode": warm_launches + args.warmup + args.steps, "decode": n_decode},
+            "full": args.full,
         }
         result.update(roundtrip)
-        if not args.no_cpu and world == 1 and args.workload == "c4":
+        if args.full and not args.no_cpu and world == 1 and args.workload == "c4":
             cores, aff, quota, model = host_cores()
             slab = field_t.cpu().numpy()
             cb = cpu_baseline_chunk(slab, 512, rank * 64)
@@ -503,7 +561,7 @@ def main():
             else:
                 result["cpu_baseline"] = None
             del slab
-        if not args.no_cpu and world == 1 and args.workload != "c4":
+        if args.full and not args.no_cpu and world == 1 and args.workload != "c4":
             cores, aff, quota, model = host_cores()
             planes = wl["sample_planes"]
             sample_t = field_t if planes is None else field_t[:planes]
@@ -559,11 +617,13 @@ def dry_run(args, torch, dist, world, rank):
         t = torch.tensor([ms])
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ms = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_arrays(args.dump_outputs, {"copy": dst})
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": round(world * src.nbytes / (ms * 1e-3) / 1e9, 3), "unit": "GB/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-                          "data": "synthetic", "dry_run": True,
+                          "data": "synthetic", "dry_run": True, "full": args.full,
                           "config": {"workload": "dry run of --workload %s: numpy copy of 4 MiB per rank "
                                                  "(no codec, no GPU)" % args.workload}}),
               flush=True)

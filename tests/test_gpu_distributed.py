@@ -5,7 +5,7 @@
 * nccl (RCCL), world 1: the device-resident path -- chunk streams compressed
   straight into HBM buffers and gathered device to device -- gives the same
   bytes.  (RCCL cannot put two ranks on one GPU; the 8-GPU gather is timed by
-  bench.py --workload c4 under torch.distributed.run.)
+  bench.py --full --workload c4 under torch.distributed.run.)
 """
 import multiprocessing as mp
 import os

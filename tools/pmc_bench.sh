@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-call HBM traffic of a bench.py workload: one rocprofv3 --pmc run per
 # counter group (kernel trace only) over
-#   python bench.py --workload W --steps 2 --warmup 0 --clock-warm-ms 0 --no-cpu
+#   python bench.py --workload W --steps 2 --warmup 0 --clock-warm-ms 0 --full --no-cpu
 # then tools/pmc_summary.py with that run's bench line (workload, field, call
 # counts).  usage: tools/pmc_bench.sh TAG WORKLOAD [--sq]
 # Writes gpurun_out/pmc_TAG_W/{p*,bench.json,summary.json,summary.txt}; copy
@@ -21,7 +21,7 @@ i=0
 for grp in "${PASSES[@]}"; do
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $grp --output-format csv -d $OUT/p$i -o run -- \
-    python3 $R/bench.py --workload $W --steps 2 --warmup 0 --clock-warm-ms 0 --no-cpu > $OUT/p$i.log 2>&1 \
+    python3 $R/bench.py --workload $W --steps 2 --warmup 0 --clock-warm-ms 0 --full --no-cpu > $OUT/p$i.log 2>&1 \
     || { echo "pass $i ($grp) failed"; tail -5 $OUT/p$i.log; exit 1; }
   [ $i = 1 ] && grep '^{' $OUT/p1.log | tail -1 > $OUT/bench.json
   echo "pass $i ok"
