@@ -129,7 +129,10 @@ int zfp_hip_index_set_offsets(zfp_hip_index* index, const zfp_hip_job* job, cons
  * Timing of the most recent zfp_hip_compress/zfp_hip_decompress on this
  * thread, from HIP events recorded on the stream the kernels ran on:
  * kernel_ms = the codec kernel alone, total_ms = everything enqueued by the
- * call (staging copies, fix-ups, kernel).  Returns 0 if no call has run.
+ * call (staging copies, fix-ups, kernel).  A compress whose field and stream
+ * are both in device memory and that queues the codec kernel alone (aligned
+ * fixed rate at a word-aligned start) records one event pair: total_ms is then
+ * equal to kernel_ms.  Returns 0 if no call has run.
  */
 int zfp_hip_last_timing(double* kernel_ms, double* total_ms);
 

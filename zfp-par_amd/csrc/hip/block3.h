@@ -60,6 +60,9 @@ struct BlockPos {
   bool full;
 };
 
+// NOPART: the caller knows that the box has no partial block (every extent a
+// multiple of 4, no_partial_blocks below): no extent arithmetic, full = true.
+template <bool NOPART = false>
 __device__ __forceinline__ BlockPos block_pos(const Geometry& g, uint64_t b64, int dims)
 {
   BlockPos p;
@@ -77,12 +80,42 @@ __device__ __forceinline__ BlockPos block_pos(const Geometry& g, uint64_t b64, i
         b = q;
       }
       uint64_t x = g.f[a] + 4ull * bi;
-      uint64_t left = g.n[a] - x;
-      p.cnt[a] = left < 4 ? (int)left : 4;
-      p.full = p.full && left >= 4;
+      if constexpr (!NOPART) {
+        uint64_t left = g.n[a] - x;
+        p.cnt[a] = left < 4 ? (int)left : 4;
+        p.full = p.full && left >= 4;
+      }
       p.off += (int64_t)x * g.s[a];
     }
   }
+  return p;
+}
+
+// every block of the 3D chunk box lies inside the field
+__host__ __device__ inline bool no_partial_blocks3(const Geometry& g)
+{
+  for (int a = 0; a < 3; a++)
+    if (g.f[a] + 4ull * g.nb[a] > g.n[a])
+      return false;
+  return true;
+}
+
+// Block positions of a wave whose 64 blocks lie in one x-row (blocks per row a
+// multiple of 64, `first` a multiple of 64 and wave-uniform): the row's
+// coordinates come from one division chain on the scalar unit, a lane adds its
+// x offset.  Same addresses as block_pos<true>(g, first + lane, 3).
+__device__ __forceinline__ BlockPos block_pos_row3(const Geometry& g, uint32_t first, uint32_t lane)
+{
+  const uint32_t q0 = fastdiv(first, g.dv[0]);
+  const uint32_t bx = first - q0 * g.nb[0];
+  const uint32_t bz = fastdiv(q0, g.dv[1]);
+  const uint32_t by = q0 - bz * g.nb[1];
+  const int64_t row = (int64_t)(g.f[0] + 4ull * bx) * g.s[0] + (int64_t)(g.f[1] + 4ull * by) * g.s[1] +
+                      (int64_t)(g.f[2] + 4ull * bz) * g.s[2];
+  BlockPos p;
+  p.off = row + (int64_t)(4u * lane) * g.s[0];
+  p.cnt[0] = p.cnt[1] = p.cnt[2] = p.cnt[3] = 4;
+  p.full = true;
   return p;
 }
 
@@ -128,12 +161,14 @@ __device__ __forceinline__ void store16(S* p, const Vec16<S, N>& q)
 #endif
 }
 
-template <typename S, bool VEC>
+// NOPART: every block is full (block_pos<true>, block_pos_row3): the padded
+// gather is not compiled, so there are no two bodies to merge.
+template <typename S, bool VEC, bool NOPART = false>
 __device__ __forceinline__ void gather3(S (&v)[64], const S* __restrict__ base, const Geometry& g, const BlockPos& p)
 {
   const S* o = base + p.off;
   const int64_t sx = g.s[0], sy = g.s[1], sz = g.s[2];
-  if (p.full) {
+  if (NOPART || p.full) {
 #pragma unroll
     for (int k = 0; k < 4; k++)
 #pragma unroll
@@ -248,6 +283,105 @@ __device__ __forceinline__ void planes_from_coeffs(uint32_t (&Pl)[32], uint32_t 
   }
   transpose32_nb(Pl);
   transpose32_nb(Ph);
+}
+
+// Narrow high half.  On smooth data the transform leaves coefficients 32..63
+// (coding order) a few bits wide, so planes 8..31 of the high half are zero in
+// every lane of the wave and need neither the transpose nor registers.  A lane
+// is narrow when every high coefficient has its negabinary form (x + K) ^ K
+// below 2^8, i.e. x in [-170, 85]: then x + K = 0xaaaaaa00 + low byte.  The test
+// is exact (one three-input OR per coefficient of the bits that differ from K);
+// the caller ballots it, since the plane arrays' shape is a wave-level choice.
+// (ZFP_NARROW_HI=0: A/B builds without the narrow path)
+#ifndef ZFP_NARROW_HI
+#define ZFP_NARROW_HI 1
+#endif
+
+// [B, E): the coefficients tested (coding order)
+template <bool P3 = true, int B = 32, int E = 64>
+__device__ __forceinline__ bool high_half_narrow(const int32_t (&q)[64])
+{
+  uint32_t acc = 0;
+#pragma unroll
+  for (int i = B; i < E; i++)  // acc |= (x + K) ^ K
+    acc = __builtin_amdgcn_bitop3_b32(acc, (uint32_t)q[P3 ? kPerm3[i] : i] + 0xaaaaaaaau, 0xaaaaaaaau, 0xf6);
+  return acc < 256u;
+}
+
+// High-half planes of a wave in which every lane is narrow: the 32 low bytes of
+// x + K packed into 8 words (word j: coefficients 32 + j, 40 + j, 48 + j,
+// 56 + j) and the bit steps only (transpose8x4_nb): 24 + 48 instructions for
+// 256.  Ph[8..31] are constant zeros.
+template <bool P3 = true>
+__device__ __forceinline__ void planes_high_narrow(uint32_t (&Ph)[32], const int32_t (&q)[64])
+{
+  uint32_t W[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    uint32_t a[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      a[b] = nb_planes((uint32_t)q[P3 ? kPerm3[32 + 8 * b + j] : 32 + 8 * b + j] + 0xaaaaaaaau);
+    // byte 0 of a[0], a[1] | byte 0 of a[2], a[3], then the low halves of both
+    const uint32_t t0 = __builtin_amdgcn_perm(a[1], a[0], 0x05010400u);
+    const uint32_t t1 = __builtin_amdgcn_perm(a[3], a[2], 0x05010400u);
+    W[j] = __builtin_amdgcn_perm(t1, t0, 0x05040100u);
+  }
+  transpose8x4_nb(W);
+#pragma unroll
+  for (int k = 0; k < 32; k++)
+    Ph[k] = k < 8 ? W[k] : 0u;
+}
+
+template <bool P3 = true>
+__device__ __forceinline__ void planes_high_full(uint32_t (&Ph)[32], const int32_t (&q)[64])
+{
+#pragma unroll
+  for (int i = 0; i < 32; i++)
+    Ph[i] = nb_planes((uint32_t)q[P3 ? kPerm3[i + 32] : i + 32] + 0xaaaaaaaau);
+  transpose32_nb(Ph);
+}
+
+template <bool P3 = true>
+__device__ __forceinline__ void planes_low(uint32_t (&Pl)[32], const int32_t (&q)[64])
+{
+#pragma unroll
+  for (int i = 0; i < 32; i++)
+    Pl[i] = nb_planes((uint32_t)q[P3 ? kPerm3[i] : i] + 0xaaaaaaaau);
+  transpose32_nb(Pl);
+}
+
+// planes_from_coeffs with the high half narrow (every lane of the wave passes
+// high_half_narrow): the same 64 plane words
+template <bool P3 = true>
+__device__ __forceinline__ void planes_from_coeffs_narrow(uint32_t (&Pl)[32], uint32_t (&Ph)[32],
+                                                          const int32_t (&q)[64])
+{
+  planes_low<P3>(Pl, q);
+  planes_high_narrow<P3>(Ph, q);
+}
+
+// The float32 encoders' builder: the high half by the wave's class (the branch
+// is wave-uniform and rejoins before the coder, so the coder and its plane
+// registers are one copy; a second, narrow copy of the coder took the flagship
+// kernel from 128 to 152 VGPRs).
+template <bool P3 = true>
+__device__ __forceinline__ void planes_from_coeffs_auto(uint32_t (&Pl)[32], uint32_t (&Ph)[32],
+                                                        const int32_t (&q)[64])
+{
+  // the low half first, and materialised: with the test ahead of it the
+  // kernels held both halves' inputs across the branch (encode3_aligned 131
+  // VGPRs for 125, three waves per SIMD for four)
+  planes_low<P3>(Pl, q);
+  pin_registers(Pl);
+  // two stages: coefficients 32..39 are the largest of the high half, so a wave
+  // of rough data leaves after 8 of the 32 ORs (the rough C2 field ran 0.85 %
+  // slower than before with the whole test ahead of the full transpose)
+  if (ZFP_NARROW_HI && __builtin_amdgcn_ballot_w64(!high_half_narrow<P3, 32, 40>(q)) == 0 &&
+      __builtin_amdgcn_ballot_w64(!high_half_narrow<P3, 40, 64>(q)) == 0)
+    planes_high_narrow<P3>(Ph, q);
+  else
+    planes_high_full<P3>(Ph, q);
 }
 
 // double: planes 32..63 from the high words; 0..31 only when `need_low`
@@ -513,7 +647,9 @@ __device__ __forceinline__ int lossy_emax_cast(int64_t (&q)[64], double (&v)[64]
 // once the block's bit planes are built and the field values are dead: the
 // pipelined kernel issues the next batch's loads there, so they fly during the
 // coder.
-template <typename S, typename Reload, typename Mid>
+// NARROW: the float32 builder takes the narrow high half when the wave has one
+// (planes_from_coeffs_auto); chosen per kernel, where the registers allow it.
+template <bool NARROW = false, typename S, typename Reload, typename Mid>
 __device__ __forceinline__ void encode_block3_fixed(OrSlot& w, const uint32_t* lut, S (&v)[64], const CodecParams& cp,
                                                     Reload&& reload, Mid&& mid)
 {
@@ -531,24 +667,31 @@ __device__ __forceinline__ void encode_block3_fixed(OrSlot& w, const uint32_t* l
   xform<3, false, false>(q);
   ZFP_PHASE_BARRIER();
   uint32_t Pl[PREC], Ph[PREC];
-  if constexpr (PREC == 32)
-    planes_from_coeffs(Pl, Ph, q);
-  else
-    planes_from_coeffs(Pl, Ph, q, true);
-  ZFP_PHASE_BARRIER();
-  pin_registers(Pl);
-  pin_registers(Ph);
-  mid();
-  if constexpr (PREC == 32)  // lut: dbl[256] then lead[256] (CoderTables)
+  if constexpr (PREC == 32) {
+    // lut: dbl[256] then lead[256] (CoderTables)
+    if constexpr (NARROW)
+      planes_from_coeffs_auto(Pl, Ph, q);
+    else
+      planes_from_coeffs(Pl, Ph, q);
+    ZFP_PHASE_BARRIER();
+    pin_registers(Pl);
+    pin_registers(Ph);
+    mid();
     code_planes_fr32(w.d(), w.jmax, lut, e ? 1 + kE : cp.maxbits, cp.maxbits, Pl, Ph);
-  else
+  } else {
+    planes_from_coeffs(Pl, Ph, q, true);
+    ZFP_PHASE_BARRIER();
+    pin_registers(Pl);
+    pin_registers(Ph);
+    mid();
     code_planes<PREC, false>(w, lut, e ? 1 + kE : cp.maxbits, cp.maxbits, mp, Pl, Ph);
+  }
 }
 
 // Encode one block into a zeroed slot; returns its length in bits including
 // minbits padding (padding bits are the slot's zeros).  FR: fixed rate with
 // maxprec >= intprec (no per-block precision limit; see code_planes).
-template <typename S, bool REV, bool FR = false, bool HI = false, typename Reload>
+template <typename S, bool REV, bool FR = false, bool HI = false, bool NARROW = false, typename Reload>
 __device__ __forceinline__ uint32_t encode_block3(OrSlot& w, const uint32_t* lut, S (&v)[64], const CodecParams& cp,
                                                   Reload&& reload)
 {
@@ -620,7 +763,7 @@ __device__ __forceinline__ uint32_t encode_block3(OrSlot& w, const uint32_t* lut
   } else {
     // lossy (encodef.c:63-90)
     if constexpr (FR && !HI) {
-      encode_block3_fixed(w, lut, v, cp, reload, [] {});
+      encode_block3_fixed<NARROW>(w, lut, v, cp, reload, [] {});
       return cp.maxbits;
     }
     uint32_t mp;

@@ -604,12 +604,15 @@ __device__ __forceinline__ U nb_planes(U x)
 // planes); ODD_BITS: the decoders' last step inverts the odd bits of every
 // output word (u ^ 0xaa..a of every coefficient, the first half of the
 // negabinary decode), in the same single bit operation.
-template <int J, bool INV_ODD = false, bool ODD_BITS = false>
-__device__ __forceinline__ void transpose_step(uint32_t (&a)[32])
+// R = 8: the bit steps (J <= 4) across 8 words transpose the 8x8 bit matrix of
+// each byte lane (transpose8x4_nb).
+template <int J, bool INV_ODD = false, bool ODD_BITS = false, int R = 32>
+__device__ __forceinline__ void transpose_step(uint32_t (&a)[R])
 {
+  static_assert(J < R, "step past the array");
   constexpr uint32_t M = (J == 4) ? 0x0f0f0f0fu : (J == 2) ? 0x33333333u : 0x55555555u;
 #pragma unroll
-  for (int k = 0; k < 32; k++) {
+  for (int k = 0; k < R; k++) {
     if (k & J)
       continue;
     const uint32_t x = a[k], y = a[k | J];
@@ -656,6 +659,18 @@ __device__ __forceinline__ void transpose32_nb(uint32_t (&a)[32])
 {
   transpose_step<16>(a);
   transpose_step<8>(a);
+  transpose_step<4>(a);
+  transpose_step<2>(a);
+  transpose_step<1, ZFP_NB_FOLD != 0>(a);
+}
+
+// encoder, 32 coefficients that fit 8 negabinary bits: a[j] holds the low
+// bytes of x + K of coefficients j, 8 + j, 16 + j, 24 + j (bytes 0..3).  The
+// three bit steps transpose each byte lane's 8x8 matrix, so a[k] becomes plane
+// k of the 32 coefficients (bit 8 b + j from byte b of word j): the byte steps
+// of transpose32_nb are the packing, and planes 8..31 are zero.
+__device__ __forceinline__ void transpose8x4_nb(uint32_t (&a)[8])
+{
   transpose_step<4>(a);
   transpose_step<2>(a);
   transpose_step<1, ZFP_NB_FOLD != 0>(a);

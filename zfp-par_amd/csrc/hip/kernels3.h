@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64 * WPG, 3) void encode3_aligned(const S* __restri
   }
   if (b < g.nblocks) {
     OrSlot os{reinterpret_cast<uint64_t*>(wslot + (size_t)lane * sdw), sdw - 1};
-    encode_block3<S, REV, true>(os, lut, v, cp, [&](S (&r)[64]) { gather3<S, VEC>(r, data, g, p); });
+    encode_block3<S, REV, true, false, true>(os, lut, v, cp, [&](S (&r)[64]) { gather3<S, VEC>(r, data, g, p); });
   }
   if (first >= g.nblocks)
     return;
@@ -229,7 +229,11 @@ __global__ __launch_bounds__(64 * WPG, 3) void encode3_aligned(const S* __restri
 // code gets its 16 loads out first) and the copy-out has no edge cases.
 // Measured 3-5 % faster than encode3_aligned on the same launch (round 4,
 // tools/exp/c2var.hip `pf0 p1`); the launcher picks it when it applies.
-template <typename S, bool VEC>
+// NOPART: the chunk box has no partial block (no_partial_blocks3; C2 again), so
+// the gather is the full-block one alone, and a wave whose blocks lie in one
+// x-row (blocks per row a multiple of 64: wave-uniform) takes its position from
+// the scalar unit (block_pos_row3).
+template <typename S, bool VEC, bool NOPART = false>
 __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restrict__ data, Geometry g, CodecParams cp,
                                                             uint64_t* __restrict__ out, uint32_t sw, uint32_t sdw,
                                                             uint32_t magic_c)
@@ -237,15 +241,19 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
   __shared__ uint32_t lut[512];  // CoderTables: dbl[256], lead[256]
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
+  const int wv = NOPART ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   uint32_t* wslot = ldsw + (size_t)wv * 64 * sdw;
   const uint64_t w = (uint64_t)blockIdx.x * kWavesPerGroup + wv;
   const uint64_t first = w * 64;
   const uint64_t b = first + lane;
   S v[64];
   __builtin_amdgcn_s_setprio(1);
-  const BlockPos p = block_pos(g, b, 3);
-  gather3<S, VEC>(v, data, g, p);
+  BlockPos p;
+  if (NOPART && (g.nb[0] & 63u) == 0)
+    p = block_pos_row3(g, (uint32_t)first, (uint32_t)lane);
+  else
+    p = block_pos<NOPART>(g, b, 3);
+  gather3<S, VEC, NOPART>(v, data, g, p);
   __builtin_amdgcn_s_setprio(0);
   {
     const uint4* src = reinterpret_cast<const uint4*>(&kCoderTables);
@@ -259,7 +267,8 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
     __builtin_amdgcn_wave_barrier();
   }
   OrSlot os{reinterpret_cast<uint64_t*>(wslot + (size_t)lane * sdw), sdw - 1};
-  encode_block3<S, false, true>(os, lut, v, cp, [&](S (&r)[64]) { gather3<S, VEC>(r, data, g, p); });
+  encode_block3<S, false, true, false, NOPART>(os, lut, v, cp,
+                                               [&](S (&r)[64]) { gather3<S, VEC, NOPART>(r, data, g, p); });
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const uint32_t hw = sw >> 1, chunks = 64 * hw;

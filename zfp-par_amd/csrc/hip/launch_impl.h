@@ -13,6 +13,17 @@ void enc3_aligned_impl(const Launch& l, bool vec, const S* f, const Geometry& g,
   // whole workgroups, word-aligned start, even words per block (16-byte chunks)
   const bool full = r0 == 0 && (sw & 1) == 0 && sw >= 2 && g.nblocks % (64u * kWavesPerGroup) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15) == 0 && l.block.x == 64u * kWavesPerGroup;
+  // no partial block in the box: the full-block gather alone (per-wave
+  // position).  Unit x stride only: with 64 strided scalar loads in one body the
+  // float kernel spilled 128 bytes per lane.  float only: the double kernel is
+  // not the flagship's and has no timing of this form.
+  if constexpr (sizeof(S) == 4) {
+    if (full && vec && no_partial_blocks3(g)) {
+      hipLaunchKernelGGL((encode3_aligned_full<S, true, true>), l.grid, l.block, l.lds, l.stream, f, g, cp, out, sw,
+                         sdw, mc);
+      return;
+    }
+  }
   if (full && vec)
     hipLaunchKernelGGL((encode3_aligned_full<S, true>), l.grid, l.block, l.lds, l.stream, f, g, cp, out, sw, sdw, mc);
   else if (full)

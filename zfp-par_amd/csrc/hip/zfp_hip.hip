@@ -155,6 +155,11 @@ struct Ctx {
   uint32_t* idx_chk = nullptr;                      // set while a caller's index is being verified
   char* pin = nullptr;                              // pinned staging of small host copies (pin_take)
   size_t pin_used = 0;                              // bytes of it handed out in the current call
+  // Compress with field and stream both on the device: nothing is queued before
+  // or after the encode kernel's own events, so the call records those two only
+  // and record_timing reads the call time from them as well.
+  bool one_pair = false;
+  bool single_kernel = false;  // set by launch_encode when it queued exactly ev[1], one kernel, ev[2]
 };
 
 struct Timing {
@@ -256,11 +261,13 @@ static int h2d(Ctx* c, void* d, const void* h, size_t bytes, hipStream_t q)
 
 static Ctx* acquire_ctx(int device)
 {
-  if (device < 0) {
-    if (hipGetDevice(&device) != hipSuccess)
-      device = 0;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
+  // (already current, the usual case: no runtime call beyond the query)
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess)
+    cur = -1;
+  if (device < 0)
+    device = cur < 0 ? 0 : cur;
+  if (cur != device && hipSetDevice(device) != hipSuccess) {
     fail("hipSetDevice(%d) failed", device);
     return nullptr;
   }
@@ -271,6 +278,8 @@ static Ctx* acquire_ctx(int device)
         Ctx* c = g_idle[i];
         g_idle.erase(g_idle.begin() + (long)i);
         c->pin_used = 0;  // the previous call ended with a synchronize: its staging is free
+        c->one_pair = false;
+        c->single_kernel = false;
         return c;
       }
   }
@@ -778,6 +787,15 @@ static int run_encode4(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_out,
   return fail("zfp_hip: overflow pool exhausted with full-size slots");
 }
 
+// launch_encode queues one kernel between ev[1] and ev[2] and nothing else:
+// the aligned fixed-rate path (the condition below) at a word-aligned start
+static bool aligned_encode(const Plan& p)
+{
+  return p.type >= 3 && p.fixed && (p.cp.maxbits % 64) == 0 && p.cp.maxprec >= (p.dbl ? 64u : 32u) && p.dims == 3;
+}
+
+static bool one_kernel_encode(const Plan& p, uint32_t g0) { return g0 == 0 && aligned_encode(p); }
+
 template <typename S>
 static int launch_encode(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_out, uint32_t g0,
                          const Head& head, zfp_hip_index* index, uint64_t* total_bits)
@@ -792,7 +810,7 @@ static int launch_encode(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_ou
   // aligned fixed-rate kernel: word-multiple blocks and no precision limit
   // below the integer width (its coder runs every plane until the budget)
   if constexpr (!kIntField<S>)
-  if (p.fixed && (p.cp.maxbits % 64) == 0 && p.cp.maxprec >= (p.dbl ? 64u : 32u) && p.dims == 3) {
+  if (aligned_encode(p)) {
     const uint32_t sw = p.cp.maxbits / 64;
     const uint32_t sdw = slot_dwords_for(p.cp.maxbits) | 1u;  // dwords from 2 sw on are spare
     auto magic_of = [](uint32_t d) { return d > 1 ? (uint32_t)((0x100000000ull + d - 1) / d) : 0u; };
@@ -819,6 +837,7 @@ static int launch_encode(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_ou
       HIP_TRY(hipGetLastError());
     }
     *total_bits = p.g.nblocks * (uint64_t)p.cp.maxbits;
+    c->single_kernel = g0 == 0;
     return 1;
   }
   // general path
@@ -1121,7 +1140,7 @@ static void record_timing(Ctx* c)
 {
   float k = 0, t = 0;
   if (hipEventElapsedTime(&k, c->ev[1], c->ev[2]) == hipSuccess &&
-      hipEventElapsedTime(&t, c->ev[0], c->ev[3]) == hipSuccess) {
+      hipEventElapsedTime(&t, c->ev[c->one_pair ? 1 : 0], c->ev[c->one_pair ? 2 : 3]) == hipSuccess) {
     t_timing.kernel_ms = k;
     t_timing.total_ms = t;
     t_timing.timed = true;
@@ -1915,7 +1934,11 @@ int zfp_hip_compress(const zfp_hip_job* job, const void* field_base, uint64_t* w
       return ok;
     }
   }
-  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  // stream
+  const bool direct = dev_stream && W0 + worst_words <= capacity_words;
+  c->one_pair = dev_field && direct && one_kernel_encode(p, g0);
+  if (!c->one_pair)
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   // field
   const void* d_field = field_base;
   if (!dev_field) {
@@ -1927,9 +1950,7 @@ int zfp_hip_compress(const zfp_hip_job* job, const void* field_base, uint64_t* w
       return 0;
     d_field = d_img;
   }
-  // stream
   uint64_t* d_out;
-  const bool direct = dev_stream && W0 + worst_words <= capacity_words;
   if (direct) {
     d_out = words + W0;
   } else {
@@ -1946,6 +1967,9 @@ int zfp_hip_compress(const zfp_hip_job* job, const void* field_base, uint64_t* w
   });
   if (!ok)
     return 0;
+  // one_kernel_encode predicted the path before the launch; launch_encode says which it took
+  if (c->one_pair && !c->single_kernel)
+    return fail("zfp_hip_compress: internal: the encode queued more than one kernel on the two-event path");
   const uint64_t end = bit_offset + total;
   const uint64_t nwords = (g0 + total + 63) / 64;
   if (W0 + nwords > capacity_words)
@@ -1957,7 +1981,8 @@ int zfp_hip_compress(const zfp_hip_job* job, const void* field_base, uint64_t* w
     staged = dev_stream ? nullptr : pin_take(c, nwords * 8);
     HIP_TRY(hipMemcpyAsync(staged ? (void*)staged : (void*)(words + W0), d_out, nwords * 8, kind, c->stream));
   }
-  HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+  if (!c->one_pair)
+    HIP_TRY(hipEventRecord(c->ev[3], c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (staged)
     memcpy(words + W0, staged, nwords * 8);
