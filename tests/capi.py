@@ -217,13 +217,14 @@ class ZfpCAPI:
         return bytes(buf[:n])
 
     def decompress(self, data, shape, dtype, mode, param=None, ztype=None, header=False, out=None,
-                   execution=None, index=None):
+                   execution=None, index=None, strided=False):
+        """`strided`: the field takes `out`'s own strides (a transposed or sliced array)."""
         dtype = np.dtype(dtype)
         if out is None:
             out = np.zeros(shape, dtype=dtype)
         if ztype is None:
             ztype = TYPE_OF[dtype]
-        field = self.field_for(out)
+        field = self.field_for(out, strided)
         zs = self.lib.zfp_stream_open(None)
         self.set_mode(zs, mode, param, ztype, len(shape))
         if execution is not None:

@@ -1,4 +1,4 @@
-"""Host slab pipeline (zfp_hip.hip compress_slabs / decompress_slabs).
+"""Host slab pipeline (host_pipeline.h compress_slabs / decompress_slabs).
 
 A host-resident field and stream go through the GPU in slabs of whole block
 layers, with uploads, kernels and downloads overlapped on three streams.  The
