@@ -1010,6 +1010,8 @@ __device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, 
 #pragma unroll
   for (int k = 31; k >= 0; k--) {
     if (m32) {
+      // (a narrow wave has Ph[8..31] == 0, but skipping their test on a
+      // wave-uniform flag measured slower than testing them: DESIGN 4.2)
       if (__builtin_amdgcn_ballot_w64(Ph[k] != 0u || n > 31u) != 0) {
         m32 = false;
         ksw = k;
@@ -1021,7 +1023,11 @@ __device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, 
         const uint32_t l1 = *lds_at(tdbl + byte1_x4(xs));
         const uint32_t bl = 32u - (uint32_t)__clz((int)xs);
         const uint32_t e1 = (uint32_t)__popc(xs) + bl;
-        fr_write32(Q, ubfe(pl, 0u, n));  // the n verbatim bits
+        // the n verbatim bits; none in the first plane (n == 0), where the OR
+        // of a constant zero would still be issued as two LDS reads, each
+        // waited for, ahead of the table look-ups
+        if (k != 31)
+          fr_write32(Q, ubfe(pl, 0u, n));
         const int32_t Qg = Q - (int32_t)n;
         const uint32_t d = (l1 << (l0 & 31u)) | (l0 >> 5);  // (dbl(xs & 0xffff) << 1 | 1) mod 2^32
         uint32_t g = d - (1u << (e1 & 31u));

@@ -233,11 +233,28 @@ __global__ __launch_bounds__(64 * WPG, 3) void encode3_aligned(const S* __restri
 // the gather is the full-block one alone, and a wave whose blocks lie in one
 // x-row (blocks per row a multiple of 64: wave-uniform) takes its position from
 // the scalar unit (block_pos_row3).
-template <typename S, bool VEC, bool NOPART = false>
+// SW: words per block at compile time (0: the run-time sw, sdw and magic_c).
+// With SW the slot stride is kAlignedSlotDwords<SW> (the launcher checks that
+// the sdw it was handed is that one), the slot zero-fill and the copy-out are
+// unrolled, and a lane's LDS and stream addresses are one base plus
+// immediates: chunk c = lane + 64 i of the run lies in slot
+// (lane / hw) + i (64 / hw), hw = SW / 2 a power of two, at quad lane % hw.
+// All of a lane's LDS reads are issued before the first store waits for one.
+// Same blocks, same bits, same slots.  (The same constants in encode3_aligned
+// for rate 8 behind a header did not beat its run-time form on C4: not kept,
+// DESIGN 4.2.)
+template <int SW>
+constexpr uint32_t kAlignedSlotDwords = slot_dwords_for(64u * SW) | 1u;
+
+template <typename S, bool VEC, bool NOPART = false, int SW = 0>
 __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restrict__ data, Geometry g, CodecParams cp,
-                                                            uint64_t* __restrict__ out, uint32_t sw, uint32_t sdw,
+                                                            uint64_t* __restrict__ out, uint32_t sw_, uint32_t sdw_,
                                                             uint32_t magic_c)
 {
+  constexpr uint32_t kHw = SW / 2;  // 16-byte chunks per slot
+  static_assert(SW == 0 || (SW % 2 == 0 && kHw <= 64 && (kHw & (kHw - 1)) == 0), "SW: 2 hw, hw a power of two");
+  const uint32_t sw = SW ? (uint32_t)SW : sw_;
+  const uint32_t sdw = SW ? kAlignedSlotDwords<SW> : sdw_;
   __shared__ uint32_t lut[512];  // CoderTables: dbl[256], lead[256]
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
@@ -261,8 +278,17 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
     dst[lane] = src[lane];
     dst[lane + 64] = src[lane + 64];
     uint4* z = reinterpret_cast<uint4*>(wslot);
-    for (uint32_t i = lane; i < 16 * sdw; i += 64)
-      z[i] = make_uint4(0, 0, 0, 0);
+    if constexpr (SW != 0) {
+      constexpr uint32_t kQuads = 16 * kAlignedSlotDwords<SW>;  // of the wave's 64 slots
+#pragma unroll
+      for (uint32_t i = 0; i < kQuads / 64; i++)
+        z[lane + 64 * i] = make_uint4(0, 0, 0, 0);
+      if (kQuads % 64 != 0 && (uint32_t)lane < kQuads % 64)
+        z[lane + (kQuads & ~63u)] = make_uint4(0, 0, 0, 0);
+    } else {
+      for (uint32_t i = lane; i < 16 * sdw; i += 64)
+        z[i] = make_uint4(0, 0, 0, 0);
+    }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) only
     __builtin_amdgcn_wave_barrier();
   }
@@ -271,17 +297,38 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
                                                [&](S (&r)[64]) { gather3<S, VEC, NOPART>(r, data, g, p); });
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  const uint32_t hw = sw >> 1, chunks = 64 * hw;
   uint64_t* dst = out + first * sw;
-  for (uint32_t c = lane; c < chunks; c += 64) {
-    const uint32_t l = div_magic(c, magic_c);
-    const uint32_t* s = wslot + (size_t)l * sdw + 4 * (c - l * hw);
+  if constexpr (SW != 0) {
+    const uint32_t ln = (uint32_t)lane;
+    const uint32_t* s = wslot + (ln / kHw) * sdw + 4 * (ln % kHw);
+    uint64_t* d = dst + 2 * ln;
+    uint32_t r[kHw][4];
+#pragma unroll
+    for (uint32_t i = 0; i < kHw; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        r[i][j] = s[i * (64 / kHw) * sdw + j];
+#pragma unroll
+    for (uint32_t i = 0; i < kHw; i++) {
 #if ZFP_NT_STORE && defined(__HIP_DEVICE_COMPILE__)
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(u4{s[0], s[1], s[2], s[3]}, reinterpret_cast<u4*>(dst + 2 * c));
+      typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+      __builtin_nontemporal_store(u4{r[i][0], r[i][1], r[i][2], r[i][3]}, reinterpret_cast<u4*>(d + 128 * i));
 #else
-    *reinterpret_cast<uint4*>(dst + 2 * c) = make_uint4(s[0], s[1], s[2], s[3]);
+      *reinterpret_cast<uint4*>(d + 128 * i) = make_uint4(r[i][0], r[i][1], r[i][2], r[i][3]);
 #endif
+    }
+  } else {
+    const uint32_t hw = sw >> 1, chunks = 64 * hw;
+    for (uint32_t c = lane; c < chunks; c += 64) {
+      const uint32_t l = div_magic(c, magic_c);
+      const uint32_t* s = wslot + (size_t)l * sdw + 4 * (c - l * hw);
+#if ZFP_NT_STORE && defined(__HIP_DEVICE_COMPILE__)
+      typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+      __builtin_nontemporal_store(u4{s[0], s[1], s[2], s[3]}, reinterpret_cast<u4*>(dst + 2 * c));
+#else
+      *reinterpret_cast<uint4*>(dst + 2 * c) = make_uint4(s[0], s[1], s[2], s[3]);
+#endif
+    }
   }
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
 }

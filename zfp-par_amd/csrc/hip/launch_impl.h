@@ -19,6 +19,13 @@ void enc3_aligned_impl(const Launch& l, bool vec, const S* f, const Geometry& g,
   // not the flagship's and has no timing of this form.
   if constexpr (sizeof(S) == 4) {
     if (full && vec && no_partial_blocks3(g)) {
+      // rate 16 with the slot stride its kernel is compiled for: the slot
+      // geometry at compile time (any other stride: the run-time form)
+      if (sw == 16 && sdw == kAlignedSlotDwords<16>) {
+        hipLaunchKernelGGL((encode3_aligned_full<S, true, true, 16>), l.grid, l.block, l.lds, l.stream, f, g, cp, out,
+                           sw, sdw, mc);
+        return;
+      }
       hipLaunchKernelGGL((encode3_aligned_full<S, true, true>), l.grid, l.block, l.lds, l.stream, f, g, cp, out, sw,
                          sdw, mc);
       return;
