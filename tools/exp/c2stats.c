@@ -5,9 +5,14 @@
  * switch to decode_plane64 for the rest of the block), and how often a
  * section reaches past the 31-bit window.  Oracle restatement of the cast,
  * transform and order.
+ * `c2stats classes [zstep]`: the encoder's plane classes (code_planes_fr32 with
+ * a PlaneClass, codec_dev.h) on every wave of the field (every zstep-th layer
+ * of blocks): per plane the share of waves in class S, M and the wide form,
+ * and the spread of both thresholds.
  * build: gcc -O2 -I../../oracle c2stats.c -lm -o /tmp/c2stats */
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "../../oracle/zfp_oracle.c"
 
 static double F(int x, int y, int z, int n)
@@ -15,8 +20,64 @@ static double F(int x, int y, int z, int n)
   return sin(0.05 * x) * cos(0.03 * y) + 0.5 * sin(0.02 * z + 0.01 * x * y / n);
 }
 
+static int bitlen_u32(uint32_t x)
+{
+  int b = 0;
+  while (x) b++, x >>= 1;
+  return b;
+}
+
+/* thresholds of planes_from_coeffs_auto<P3, true> (block3.h) from the widths of
+ * a wave's coefficients in negabinary: ksw = bitlen(c32..63 | c31 >> 1) - 1,
+ * kS = bitlen(c15..63) for a narrow wave (every c32..63 below 2^8), else 32 */
+static int classes(int n, int zstep)
+{
+  long nw = 0, narrow = 0, cls[32][3] = {{0}}, hS[34] = {0}, hW[34] = {0};
+  for (int bz = 0; bz < n / 4; bz += zstep)
+    for (int by = 0; by < n / 4; by++)
+      for (int bx0 = 0; bx0 < n / 4; bx0 += 64) {
+        uint32_t A = 0, B = 0, W = 0;
+        for (int l = 0; l < 64; l++) {
+          float v[64];
+          for (int i = 0; i < 64; i++)
+            v[i] = (float)F(4 * (bx0 + l) + (i & 3), 4 * by + ((i >> 2) & 3), 4 * bz + (i >> 4), n);
+          int emax = oz_emax_f(v, 64);
+          int32_t q[64];
+          oz_cast_fwd_f(q, v, 64, emax);
+          oz_xform_f(q, 3, 0, 0);
+          for (int i = 15; i < 64; i++) {
+            const uint32_t u = oz_to_nb_f(q[oz_perm3[i]]);
+            W |= u;
+            if (i == 31) B = B | u;
+            if (i >= 32) A |= u;
+          }
+        }
+        const int nar = A < 256u;
+        const int ksw = bitlen_u32(A | (B >> 1)) - 1;
+        int kS = nar ? bitlen_u32(W) : 32;
+        if (kS <= ksw) kS = ksw + 1;
+        nw++;
+        narrow += nar;
+        hS[kS]++;
+        hW[ksw + 1]++;
+        for (int k = 0; k < 32; k++) cls[k][k >= kS ? 0 : k > ksw ? 1 : 2]++;
+      }
+  printf("waves %ld, narrow %ld (%.2f %%)\n", nw, narrow, 100.0 * narrow / nw);
+  printf("plane  S %%     M %%     wide %%\n");
+  for (int k = 31; k >= 0; k--)
+    printf("%5d  %6.2f  %6.2f  %6.2f\n", k, 100.0 * cls[k][0] / nw, 100.0 * cls[k][1] / nw, 100.0 * cls[k][2] / nw);
+  printf("kS (waves):");
+  for (int i = 0; i <= 32; i++) if (hS[i]) printf(" %d:%ld", i, hS[i]);
+  printf("\nksw (waves):");
+  for (int i = 0; i <= 32; i++) if (hW[i]) printf(" %d:%ld", i - 1, hW[i]);
+  printf("\n");
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
+  if (argc > 1 && !strcmp(argv[1], "classes"))
+    return classes(1024, argc > 2 ? atoi(argv[2]) : 1);
   const int n = 1024, waves = argc > 1 ? atoi(argv[1]) : 400;
   srand(3);
   double planes_sum = 0, p32_sum = 0, wmax_planes = 0, long_sec = 0, slow32 = 0;

@@ -299,13 +299,18 @@ __device__ __forceinline__ void planes_from_coeffs(uint32_t (&Pl)[32], uint32_t 
 
 // [B, E): the coefficients tested (coding order)
 template <bool P3 = true, int B = 32, int E = 64>
-__device__ __forceinline__ bool high_half_narrow(const int32_t (&q)[64])
+__device__ __forceinline__ uint32_t nb_or(const int32_t (&q)[64], uint32_t acc = 0)
 {
-  uint32_t acc = 0;
 #pragma unroll
   for (int i = B; i < E; i++)  // acc |= (x + K) ^ K
     acc = __builtin_amdgcn_bitop3_b32(acc, (uint32_t)q[P3 ? kPerm3[i] : i] + 0xaaaaaaaau, 0xaaaaaaaau, 0xf6);
-  return acc < 256u;
+  return acc;
+}
+
+template <bool P3 = true, int B = 32, int E = 64>
+__device__ __forceinline__ bool high_half_narrow(const int32_t (&q)[64])
+{
+  return nb_or<P3, B, E>(q) < 256u;
 }
 
 // High-half planes of a wave in which every lane is narrow: the 32 low bytes of
@@ -365,9 +370,24 @@ __device__ __forceinline__ void planes_from_coeffs_narrow(uint32_t (&Pl)[32], ui
 // is wave-uniform and rejoins before the coder, so the coder and its plane
 // registers are one copy; a second, narrow copy of the coder took the flagship
 // kernel from 128 to 152 VGPRs).
-template <bool P3 = true>
-__device__ __forceinline__ void planes_from_coeffs_auto(uint32_t (&Pl)[32], uint32_t (&Ph)[32],
-                                                        const int32_t (&q)[64])
+//
+// CLS: also the wave's plane classes for the coder (PlaneClass, codec_dev.h),
+// from the widths of the coefficients; every lane of the wave must be active.
+// With nb(c) = (c + K) ^ K, plane k of coefficient i is bit k of nb(c_i), and a
+// lane's significance count after a plane is the bit length of the planes so
+// far, so (bitlen of the OR over the wave = the widest lane):
+//   ksw = bitlen(nb(c32..63) | nb(c31) >> 1) - 1: the first plane with a bit in
+//         the high half, or with coefficient 31 already significant;
+//   kS  = bitlen(nb(c15..63)): above it only coefficients 0..14 have bits.
+// A narrow wave takes ksw from the test's OR and coefficient 31 (four VALU and
+// one wave reduction) and kS from the low planes, top down, one compare of
+// Pl[k] with 0x7fff per plane until some lane has a bit there: the inputs of
+// the low transpose are dead by then, and keeping coefficients 15..31 for an OR
+// of their own took the kernel from 116 to 135 VGPRs.  A wide wave gets no
+// classes (ksw = kPlanesTested): its caller codes it with the per-plane test.
+template <bool P3 = true, bool CLS = false>
+__device__ __forceinline__ PlaneClass planes_from_coeffs_auto(uint32_t (&Pl)[32], uint32_t (&Ph)[32],
+                                                              const int32_t (&q)[64])
 {
   // the low half first, and materialised: with the test ahead of it the
   // kernels held both halves' inputs across the branch (encode3_aligned 131
@@ -377,11 +397,35 @@ __device__ __forceinline__ void planes_from_coeffs_auto(uint32_t (&Pl)[32], uint
   // two stages: coefficients 32..39 are the largest of the high half, so a wave
   // of rough data leaves after 8 of the 32 ORs (the rough C2 field ran 0.85 %
   // slower than before with the whole test ahead of the full transpose)
-  if (ZFP_NARROW_HI && __builtin_amdgcn_ballot_w64(!high_half_narrow<P3, 32, 40>(q)) == 0 &&
-      __builtin_amdgcn_ballot_w64(!high_half_narrow<P3, 40, 64>(q)) == 0)
+  uint32_t a = 0;
+  bool narrow = false;
+  if (ZFP_NARROW_HI) {
+    a = nb_or<P3, 32, 40>(q);
+    if (__builtin_amdgcn_ballot_w64(a >= 256u) == 0) {
+      a = nb_or<P3, 40, 64>(q, a);
+      narrow = __builtin_amdgcn_ballot_w64(a >= 256u) == 0;
+    }
+  }
+  PlaneClass pc{kPlanesTested, 32};
+  if (narrow) {
+    if constexpr (CLS) {
+      const uint32_t b = ((uint32_t)q[P3 ? kPerm3[31] : 31] + 0xaaaaaaaau) ^ 0xaaaaaaaau;
+      pc.ksw = (int)nbits32(wave_or(a | (b >> 1))) - 1;
+      pc.kS = 0;
+#pragma unroll
+      for (int k = 31; k >= 0; k--) {
+        if (__builtin_amdgcn_ballot_w64(Pl[k] > 0x7fffu) != 0) {
+          pc.kS = k + 1;
+          break;
+        }
+      }
+      pc.kS = pc.kS > pc.ksw ? pc.kS : pc.ksw + 1;
+    }
     planes_high_narrow<P3>(Ph, q);
-  else
-    planes_high_full<P3>(Ph, q);
+  } else {
+    planes_high_full<P3>(Ph, q);  // (pc stays kPlanesTested)
+  }
+  return pc;
 }
 
 // double: planes 32..63 from the high words; 0..31 only when `need_low`
@@ -649,7 +693,9 @@ __device__ __forceinline__ int lossy_emax_cast(int64_t (&q)[64], double (&v)[64]
 // coder.
 // NARROW: the float32 builder takes the narrow high half when the wave has one
 // (planes_from_coeffs_auto); chosen per kernel, where the registers allow it.
-template <bool NARROW = false, typename S, typename Reload, typename Mid>
+// NARROW == 2: the builder also classes the wave's planes for the coder (kernels
+// whose waves are whole: every lane active).
+template <int NARROW = 0, typename S, typename Reload, typename Mid>
 __device__ __forceinline__ void encode_block3_fixed(OrSlot& w, const uint32_t* lut, S (&v)[64], const CodecParams& cp,
                                                     Reload&& reload, Mid&& mid)
 {
@@ -669,15 +715,23 @@ __device__ __forceinline__ void encode_block3_fixed(OrSlot& w, const uint32_t* l
   uint32_t Pl[PREC], Ph[PREC];
   if constexpr (PREC == 32) {
     // lut: dbl[256] then lead[256] (CoderTables)
-    if constexpr (NARROW)
-      planes_from_coeffs_auto(Pl, Ph, q);
+    PlaneClass pc{kPlanesTested, 32};
+    if constexpr (NARROW != 0)
+      pc = planes_from_coeffs_auto<true, NARROW == 2>(Pl, Ph, q);
     else
       planes_from_coeffs(Pl, Ph, q);
     ZFP_PHASE_BARRIER();
     pin_registers(Pl);
     pin_registers(Ph);
     mid();
-    code_planes_fr32(w.d(), w.jmax, lut, e ? 1 + kE : cp.maxbits, cp.maxbits, Pl, Ph);
+    // a wide wave keeps the coder that tests every plane: sent through the
+    // class coder (ksw from a scan of its planes, no class S) the rough field
+    // ran 0.5-1.0 % slower than before, with this second copy 0.4 % faster
+    // 
+    if (NARROW == 2 && pc.ksw != kPlanesTested)
+      code_planes_fr32(w.d(), w.jmax, lut, e ? 1 + kE : cp.maxbits, cp.maxbits, Pl, Ph, pc);
+    else
+      code_planes_fr32(w.d(), w.jmax, lut, e ? 1 + kE : cp.maxbits, cp.maxbits, Pl, Ph);
   } else {
     planes_from_coeffs(Pl, Ph, q, true);
     ZFP_PHASE_BARRIER();
@@ -691,7 +745,7 @@ __device__ __forceinline__ void encode_block3_fixed(OrSlot& w, const uint32_t* l
 // Encode one block into a zeroed slot; returns its length in bits including
 // minbits padding (padding bits are the slot's zeros).  FR: fixed rate with
 // maxprec >= intprec (no per-block precision limit; see code_planes).
-template <typename S, bool REV, bool FR = false, bool HI = false, bool NARROW = false, typename Reload>
+template <typename S, bool REV, bool FR = false, bool HI = false, int NARROW = 0, typename Reload>
 __device__ __forceinline__ uint32_t encode_block3(OrSlot& w, const uint32_t* lut, S (&v)[64], const CodecParams& cp,
                                                   Reload&& reload)
 {

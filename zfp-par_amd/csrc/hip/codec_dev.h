@@ -995,6 +995,132 @@ __device__ __forceinline__ void code_planes_fru(OrSlot& os, const uint32_t* lut,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Plane classes of a wave (ZFP_PLANE_CLASS=0: A/B builds without them).  The
+// 32-bit body above asks every plane, with vector compares, whether the wave
+// must leave it and whether some lane needs the extension branch.  Both
+// answers follow from the widths of the wave's coefficients, so the builder
+// (planes_from_coeffs_auto, block3.h) hands over two wave-uniform thresholds
+// and a plane costs one scalar compare:
+//   k >= kS        class S: no lane has a bit of coefficients 15..63 in this
+//                  plane or above, so n' <= 15, xs <= 0x7fff (no extension) and
+//                  the plane's n + e1 + 1 <= 2 n' + 1 - n <= 31 bits are one
+//                  value, written once;
+//   kS > k > ksw   class M: the 32-bit body without its leave test;
+//   k <= ksw       code_planes_fru from plane ksw on.
+// Either threshold may be larger than needed (kS > ksw always): the later
+// forms are general.
+#ifndef ZFP_PLANE_CLASS
+#define ZFP_PLANE_CLASS 1
+#endif
+constexpr int kPlanesTested = -2;  // PlaneClass::ksw of a wave without classes
+struct PlaneClass {
+  int ksw;  // -1 .. 31: the first plane of the wide form (-1: none); or kPlanesTested
+  int kS;   // 0 .. 32: planes kS .. 31 are class S
+};
+
+__device__ __forceinline__ uint32_t nbits32(uint32_t x) { return 32u - (uint32_t)__clz((int)x); }
+
+// OR over the wave, every lane active; the result is wave-uniform (an SGPR):
+// four row shifts, two row broadcasts, one v_readlane.  (Host emulation: a
+// wave is one lane.)
+__device__ __forceinline__ uint32_t wave_or(uint32_t x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+  int v = (int)x;
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8: lane 15 of a row has the row
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return (uint32_t)__builtin_amdgcn_readlane(v, 63);
+#else
+  return x;
+#endif
+}
+
+// code_planes_fr32 with the wave's plane classes: the same bits in the same
+// slot words.  Positions as there (Q = -bit address).
+__device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, const uint32_t* lut, uint32_t pos,
+                                                 uint32_t lim, const uint32_t (&Pl)[32], const uint32_t (&Ph)[32],
+                                                 const PlaneClass& pc)
+{
+  OrSlot os{reinterpret_cast<uint64_t*>(slot), jmax};
+#if ZFP_FR32
+  const uint32_t sb = lds_off(slot) * 8u;  // slot bit address
+  const uint32_t tdbl = lds_off(lut), tlead = tdbl + 1024u;
+  int32_t Q = -(int32_t)(sb + pos);
+  const int32_t Qlim = -(int32_t)(sb + lim);
+  const int ksw = pc.ksw, kS = pc.kS;
+  uint32_t n = 0;
+  // class S: verbatim and group bits as one value v = verb | g << n with
+  // g = d - 2^e1 and verb = pl - (xs << n), i.e. pl + ((d - xs) << n) - 2^(n + e1)
+  // (no exit from the loops: left at a wave-uniform plane they have no constant
+  // trip count and are not unrolled.  The planes past ksw are skipped four at a
+  // time; a wave that is wide from the first plane on goes straight on.)
+#pragma unroll
+  for (int k4 = 28; k4 >= 0; k4 -= 4) {
+    if (ksw >= k4 + 3)
+      continue;
+#pragma unroll
+    for (int k = k4 + 3; k >= k4; k--) {
+      if (k >= kS) {
+        exp_vpad();
+        const uint32_t pl = Pl[k];
+        const uint32_t xs = k == 31 ? pl : pl >> n;
+        const uint32_t l0 = *lds_at(tlead + byte0_x4(xs));
+        const uint32_t l1 = *lds_at(tdbl + byte1_x4(xs));
+        const uint32_t n1 = (k == 31 ? 0u : n) + nbits32(xs);
+        const uint32_t ne = (uint32_t)__popc(xs) + n1;  // n + e1
+        const uint32_t d = (l1 << (l0 & 31u)) | (l0 >> 5);  // (dbl(xs & 0xffff) << 1 | 1) mod 2^32
+        const uint32_t v = k == 31 ? d - (1u << (ne & 31u)) : pl + ((d - xs) << n) - (1u << (ne & 31u));
+        fr_write32(Q, v);
+        const int32_t Qn = Q - (int32_t)ne - 1;
+        Q = Qn > Qlim ? Qn : Qlim;
+        n = n1;
+      } else if (k > ksw) {
+        // class M
+        exp_vpad();
+        const uint32_t pl = Pl[k];
+        const uint32_t xs = pl >> n;
+        const uint32_t l0 = *lds_at(tlead + byte0_x4(xs));
+        const uint32_t l1 = *lds_at(tdbl + byte1_x4(xs));
+        const uint32_t bl = nbits32(xs);
+        const uint32_t e1 = (uint32_t)__popc(xs) + bl;
+        if (k != 31)  // (n == 0: as in the form above)
+          fr_write32(Q, ubfe(pl, 0u, n));
+        const int32_t Qg = Q - (int32_t)n;
+        const uint32_t d = (l1 << (l0 & 31u)) | (l0 >> 5);
+        uint32_t g = d - (1u << (e1 & 31u));
+        const bool ext = xs > 0xfffeu;
+        if (__builtin_amdgcn_ballot_w64(ext) != 0) {
+          // rare, as in the form above
+          const uint32_t h = 31u - (uint32_t)__clz((int)xs);
+          const uint32_t gp = (uint32_t)(-Qg) - sb;
+          const uint32_t g32 = (xs & 0xffffu) == 0xffffu ? 1u : 0u;
+          g = ext ? d : g;
+          expand_event(os, lut, ExtEvent{gp, xs, 0u, ext ? h | (g32 << 7) : 0u});
+        }
+        fr_write32(Qg, g);
+        const int32_t Qn = Qg - (int32_t)e1 - 1;
+        Q = Qn > Qlim ? Qn : Qlim;
+        n += bl;
+      }
+    }
+  }
+  if (ksw >= 0) {
+#if ZFP_FRU
+    code_planes_fru(os, lut, sb, Q, Qlim, n, ksw, Pl, Ph);
+#else
+    code_planes<32, false>(os, lut, (uint32_t)(-Q) - sb, lim, 32u, Pl, Ph, ksw, n);
+#endif
+  }
+#else
+  code_planes<32, false>(os, lut, pos, lim, 32u, Pl, Ph);
+#endif
+}
+
 __device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, const uint32_t* lut, uint32_t pos,
                                                  uint32_t lim, const uint32_t (&Pl)[32], const uint32_t (&Ph)[32])
 {

@@ -293,8 +293,9 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
     __builtin_amdgcn_wave_barrier();
   }
   OrSlot os{reinterpret_cast<uint64_t*>(wslot + (size_t)lane * sdw), sdw - 1};
-  encode_block3<S, false, true, false, NOPART>(os, lut, v, cp,
-                                               [&](S (&r)[64]) { gather3<S, VEC, NOPART>(r, data, g, p); });
+  // (whole waves: the builder may class the planes for the coder)
+  encode_block3<S, false, true, false, NOPART ? 1 + ZFP_PLANE_CLASS : 0>(
+    os, lut, v, cp, [&](S (&r)[64]) { gather3<S, VEC, NOPART>(r, data, g, p); });
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   uint64_t* dst = out + first * sw;
