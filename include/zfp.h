@@ -296,6 +296,14 @@ size_t zfp_compress(zfp_stream* stream, const zfp_field* field);
 size_t zfp_compress_chunk(zfp_stream* stream, const zfp_chunk* chunk, const zfp_field* field);
 size_t zfp_decompress(zfp_stream* stream, zfp_field* field);
 size_t zfp_decompress_chunk(zfp_stream* stream, const zfp_chunk* chunk, zfp_field* field);
+/* MI355X addition: region decode.
+ * Decode region [f,e) of `region` from the stream that codes `coded` (NULL: the whole field) of `field`
+ * (type, extents; its data pointer is not used) into `out`, a field of the region's extents with its own
+ * pointer and strides.  The stream must be positioned at the first block (after any header), as for
+ * zfp_decompress_chunk; its position is left unchanged.  Only the blocks that intersect the region are
+ * decoded; 1D to 3D fields.  zfp_true on success. */
+zfp_bool zfp_decompress_region(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
+                               const zfp_chunk* region, zfp_field* out);
 /* zfp.h:797-838: dispatch with an explicit execution policy, strided flag,
  * dimensionality and scalar type (zfp_compress_chunk derives them) */
 size_t zfp_compress_call(zfp_stream* stream, const zfp_chunk* chunk, const zfp_field* field, const uint exec,

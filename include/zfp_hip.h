@@ -94,6 +94,36 @@ int zfp_hip_decompress(const zfp_hip_job* job, void* field_base, const uint64_t*
                        const zfp_hip_index* index, uint64_t* end_bit);
 
 /*
+ * Region decode: write the elements [lo, hi) of the field -- any sub-box of the
+ * coded box [f, e) of `job`, element-granular, f <= lo < hi <= e per axis --
+ * exactly as zfp_hip_decompress of the whole box would, decoding only the
+ * blocks that intersect the region.  `job` gives the coded box and the codec
+ * parameters (job->s is not used); the stream's first block is at bit
+ * `bit_offset` of `words`.  `dst` (host or device memory) receives element x
+ * at dst[sum over axes of (x - lo) * dst_stride] (element strides; entries of
+ * lo, hi and dst_stride from job->dims on are not read); nothing else is
+ * written.  1D to 3D; a 4D job returns 0.  A null pointer, an empty region or
+ * one outside the coded box, a 4D job and more than 2^32 - 1 region blocks
+ * return 0 before any GPU call, with `dst` untouched.
+ * Variable rate: `index` as for zfp_hip_decompress (NULL or not made for this
+ * stream: the stream is scanned first); the decoded length of every block read
+ * is checked against the index, and a stale index is replaced by a scan
+ * (zfp_hip_last_stale_index).  The per-block start table made from the index
+ * is kept in it for later calls.
+ * Host `words`: a fixed-rate call copies to the device only the words from the
+ * first needed block's start to the last needed block's end (plus one word of
+ * look-ahead); a variable-rate call stages the whole stream, as
+ * zfp_hip_decompress does.
+ * *blocks_read (optional) receives the number of blocks staged and decoded:
+ * the product over axes of (hi - 1 - f) / 4 - (lo - f) / 4 + 1.
+ * zfp_hip_last_timing reports the region kernel as it does any decode.
+ */
+int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4],
+                              void* dst, const int64_t dst_stride[4],
+                              const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
+                              int device, const zfp_hip_index* index, uint64_t* blocks_read);
+
+/*
  * Build the block index of the variable-rate stream at `words` for the chunk
  * box of `job`, blocks starting at bit `bit_offset` (a parallel parse of the
  * stream on the GPU; see scan.h).  Returns 0 for fixed-rate jobs, truncated

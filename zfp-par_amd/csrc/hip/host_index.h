@@ -33,10 +33,18 @@ struct zfp_hip_index : IndexView {
   int32_t minexp = 0;
   int32_t type = 0, dims = 0;
   size_t cap_blocks = 0, cap_waves = 0;
+  // Start table of the region decoder (host_region.h): the start bit of every
+  // block, 8 bytes each.  A cache of what d_len and d_base say, so a call that
+  // only reads the index may build it: built on first use, dropped whenever
+  // the arrays are about to be refilled (index_reserve), freed in index_release.
+  mutable uint64_t* d_start = nullptr;
+  mutable size_t cap_start = 0;
+  mutable bool start_valid = false;
 };
 
 static int index_reserve(zfp_hip_index* x, uint64_t nblocks, uint64_t nwaves)
 {
+  x->start_valid = false;  // whoever refills the arrays reserves first
   if (x->cap_blocks < nblocks) {
     if (x->d_len) (void)hipFree(x->d_len);
     x->d_len = nullptr;
@@ -60,9 +68,12 @@ static void index_release(zfp_hip_index* x)
 {
   if (x->d_len) (void)hipFree(x->d_len);
   if (x->d_base) (void)hipFree(x->d_base);
+  if (x->d_start) (void)hipFree(x->d_start);
   x->d_len = nullptr;
   x->d_base = nullptr;
-  x->cap_blocks = x->cap_waves = 0;
+  x->d_start = nullptr;
+  x->cap_blocks = x->cap_waves = x->cap_start = 0;
+  x->start_valid = false;
   x->nblocks = x->nwaves = 0;
   x->start_bit = ~0ull;
   x->fp = 0;

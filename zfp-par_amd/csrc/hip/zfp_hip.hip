@@ -25,6 +25,7 @@
 #include "host_launch.h"       // encode and decode launchers
 #include "host_scan.h"         // index scan of a stream without an index
 #include "host_pipeline.h"     // host <-> device box copies, the slab pipeline
+#include "host_region.h"       // region decode: validation, start table, launch, copy-out
 
 // ---------------------------------------------------------------------------
 // How every entry point that uses the device begins: the job's plan, the
@@ -315,6 +316,45 @@ int zfp_hip_decompress(const zfp_hip_job* job, void* field_base, const uint64_t*
     if (ok && stale)
       return fail("zfp_hip_decompress: decoded block lengths disagree with the stream's plain scan (corrupt stream)");
   }
+  return lease.done(ok);
+}
+
+int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4], void* dst,
+                              const int64_t dst_stride[4], const uint64_t* words, uint64_t capacity_words,
+                              uint64_t bit_offset, int device, const zfp_hip_index* index, uint64_t* blocks_read)
+{
+  // (not begin_call: the job's strides are unused and everything is validated
+  // before the first GPU call, the device count included)
+  Plan p;
+  RegionGeom rg;
+  if (!plan_region(job, lo, hi, dst, dst_stride, words, p, rg))
+    return 0;
+  if (zfp_hip_device_count() <= 0)
+    return fail("zfp_hip_decompress_region: no HIP device available");
+  CtxLease lease;
+  lease.c = acquire_ctx(device);
+  if (!lease.c)
+    return 0;
+  Ctx* c = lease.c;
+  t_timing = Timing{};
+  bool stale = false, scanned = false;
+  auto once = [&](const zfp_hip_index* x, bool plain) {
+    stale = false;
+    return region_once(c, p, rg, dst, dst_stride, words, capacity_words, bit_offset, x, plain, &stale, &scanned);
+  };
+  int ok = once(index, false);
+  if (ok && stale) {  // as zfp_hip_decompress: scan, then a scan of plain passes
+    const bool plain = scanned;
+    ok = once(nullptr, plain);
+    if (ok && stale && !plain)
+      ok = once(nullptr, true);
+    t_timing.stale_index = true;
+    if (ok && stale)
+      return fail("zfp_hip_decompress_region: decoded block lengths disagree with the stream's plain scan "
+                  "(corrupt stream)");
+  }
+  if (ok && blocks_read)
+    *blocks_read = rg.nrblocks;
   return lease.done(ok);
 }
 

@@ -1163,6 +1163,60 @@ static size_t decompress_exec(zfp_stream* zfp, const zfp_chunk* chunk, zfp_field
   return stream_size(s);
 }
 
+/* Region decode (no reference equivalent): the blocks of `coded` that intersect
+ * `region`, written into `out` -- zfp_hip_decompress_region with the stream's
+ * attached index, its device and its bit position, which stays where it is. */
+zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
+                               const zfp_chunk* region, zfp_field* out)
+{
+  bitstream* s;
+  zfp_hip_job job;
+  zfp_chunk whole;
+  zfp_hip_index* index = NULL;
+  ptrdiff_t st[4];
+  uint64 lo[4], hi[4];
+  int64_t ds[4];
+  uint d;
+  if (!zfp || !zfp->stream || !field || !region || !out || !out->data)
+    return zfp_false;
+  s = zfp->stream;
+  d = zfp_field_dimensionality(field);
+  if (field->type != out->type || zfp_field_dimensionality(out) != d)
+    return zfp_false;
+  if (!coded) {
+    whole.fx = whole.fy = whole.fz = whole.fw = 0;
+    whole.ex = field->nx;
+    whole.ey = field->ny;
+    whole.ez = field->nz;
+    whole.ew = field->nw;
+    coded = &whole;
+  }
+  {
+    const size_t f[4] = {region->fx, region->fy, region->fz, region->fw};
+    const size_t e[4] = {region->ex, region->ey, region->ez, region->ew};
+    const size_t n[4] = {out->nx, out->ny, out->nz, out->nw};
+    field_strides(out, st);
+    for (uint a = 0; a < 4; a++) {
+      lo[a] = a < d ? f[a] : 0;
+      hi[a] = a < d ? e[a] : 0;
+      ds[a] = a < d ? (int64_t)st[a] : 0;
+      if (a < d && (e[a] <= f[a] || e[a] - f[a] != n[a]))
+        return zfp_false;
+    }
+  }
+  job_from(&job, zfp, coded, field);
+  if (variable_rate(zfp, field)) {
+    ext_entry* x = ext_find(zfp, 0);
+    index = x ? x->index : NULL;
+  }
+  if (!zfp_hip_decompress_region(&job, lo, hi, out->data, ds, s->begin, (uint64)(s->end - s->begin), stream_rtell(s),
+                                 stream_device(zfp), index, NULL)) {
+    report("zfp_decompress_region");
+    return zfp_false;
+  }
+  return zfp_true;
+}
+
 /* One block of the low-level API (encode.c / decode.c templates: zfp_encode_
  * block_*, zfp_decode_block_*): the same GPU call as a chunk, on a field that
  * is the block, at the stream's bit position -- pending bits of a partly

@@ -21,7 +21,8 @@ from multiprocessing.sharedctypes import RawArray
 
 import numpy as np
 
-from .zfpy_c import _compress_portion, _decompress_portion, device_count, zfp_chunkit
+from .zfpy_c import (_compress_portion, _decompress_portion, _decompress_region_stream, _region_box, device_count,
+                     zfp_chunkit)
 
 _TYPECODE = {"float32": "f", "float64": "d", "int32": "i", "int64": "q"}
 _ITEMSIZE = {"float32": 4, "float64": 8, "int32": 4, "int64": 8}
@@ -117,6 +118,39 @@ class zfp_p:
 
         with ThreadPool(processes=max(1, min(nthreads, len(data) or 1))) as pool:
             pool.map(one, range(len(data)))
+
+    def decompress_region(self, region, nthreads=-1):
+        """The elements `region` of the compressed array as a new ndarray of the region's shape,
+        decoding only the blocks that intersect it; the shared array is not touched.  region: one
+        slice per axis in numpy order (step 1 or None, no negative indices; None: the whole axis).
+        Every chunk whose box intersects the region decodes its part of it on the thread pool, with
+        the chunk's kept block index, as decompress() does."""
+        if nthreads == -1:
+            nthreads = cpu_count()
+        data = self._compress_data
+        ck = self._chunkit
+        if len(data) != ck.get_nchunks():
+            raise RuntimeError("no compressed data for this partition (call compress first)")
+        nd = ck.ndim
+        box = _region_box(region, tuple(ck.ns_python))
+        out = np.empty(tuple(e - f for f, e in box), dtype=ck.dtype)
+        tasks = []
+        for i in range(len(data)):
+            coded = list(reversed(ck.boxes[i][:nd]))  # numpy axis order
+            part = [(max(f, cf), min(e, ce)) for (f, e), (cf, ce) in zip(box, coded)]
+            if all(f < e for f, e in part):
+                tasks.append((i, coded, part))
+
+        def one(i, coded, part):
+            blob = getattr(data[i], "block_index", None)
+            if blob is None and i < len(self._index_of) and self._index_of[i][0] is data[i]:
+                blob = self._index_of[i][1]
+            view = out[tuple(slice(f - f0, e - f0) for (f, e), (f0, _) in zip(part, box))]
+            _decompress_region_stream(data[i], coded, part, view, self._device_of(i), blob)
+
+        with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
+            pool.starmap(one, tasks)
+        return out
 
 
 def write_json_header(filename, dimensions, block_splits, compressed_files):

@@ -60,6 +60,7 @@ for _name, _res, _args in [
     ("zfp_field_set_stride_4d", None, [_vp, _pd, _pd, _pd, _pd]),
     ("zfp_compress", _sz, [_vp, _vp]), ("zfp_decompress", _sz, [_vp, _vp]),
     ("zfp_compress_chunk", _sz, [_vp, _vp, _vp]), ("zfp_decompress_chunk", _sz, [_vp, _vp, _vp]),
+    ("zfp_decompress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
     ("zfp_write_header", _sz, [_vp, _vp, _u32]), ("zfp_read_header", _sz, [_vp, _vp, _u32]),
     ("zfp_optimal_parts_from_size", _vp, [_i32, _vp, ctypes.c_float, _i32]),
     ("zfp_chunks_from_blocks", _vp, [_i32, _vp, _vp]), ("zfp_blocks_free", None, [_vp]),
@@ -454,6 +455,104 @@ def decompress_numpy(compressed_data, *, device=-1):
         _lib.zfp_field_free(field)
         _lib.zfp_stream_close(stream)
         _lib.stream_close(bstream)
+
+
+def _region_box(region, shape):
+    """`region` (one slice per numpy axis; None or slice(None): the whole axis;
+    step 1 or None, no negative indices) as [(first, end)] per numpy axis."""
+    if region is None:
+        region = (None,) * len(shape)
+    if isinstance(region, slice):
+        region = (region,)
+    region = tuple(region)
+    if len(region) != len(shape):
+        raise ValueError("region has %d slices, the array has %d axes" % (len(region), len(shape)))
+    box = []
+    for sl, n in zip(region, shape):
+        if sl is None:
+            sl = slice(None)
+        if not isinstance(sl, slice):
+            raise TypeError("region entries must be slices or None")
+        if sl.step not in (None, 1):
+            raise ValueError("region slices must have step 1")
+        f = 0 if sl.start is None else int(sl.start)
+        e = n if sl.stop is None else int(sl.stop)
+        if f < 0 or e < 0:
+            raise ValueError("region slices must not use negative indices")
+        if not f < e <= n:
+            raise ValueError("region slice %d:%d is empty or outside an axis of %d elements" % (f, e, n))
+        box.append((f, e))
+    return box
+
+
+def _chunk_of(box_xfirst):
+    """_Chunk of [(first, end)] per axis, x first."""
+    ck = _Chunk()
+    for (f, e), ax in zip(box_xfirst, "xyzw"):
+        setattr(ck, "f" + ax, f)
+        setattr(ck, "e" + ax, e)
+    return ck
+
+
+def _decompress_region_into(stream, field, coded, box, out, blob):
+    """zfp_decompress_region of `box` ([(first, end)] per numpy axis) into the
+    ndarray `out` of the box's shape, from a stream positioned after its header.
+    coded: _Chunk of what the stream codes (None: the whole field)."""
+    ck = _chunk_of(list(reversed(box)))
+    ofield = _make_field(out.ctypes.data, dtype_to_ztype(out.dtype), list(reversed(out.shape)),
+                         [s // out.itemsize for s in reversed(out.strides)])
+    idx = _attach_index(stream, blob)
+    try:
+        ret = _lib.zfp_decompress_region(stream, field, ctypes.byref(coded) if coded is not None else None,
+                                         ctypes.byref(ck), ofield)
+    finally:
+        if idx:
+            _lib.zfp_stream_set_hip_index(stream, None)
+            _lib.zfp_hip_index_free(idx)
+        _lib.zfp_field_free(ofield)
+    if not ret:
+        raise RuntimeError("error during zfp region decompression")
+    return out
+
+
+def _decompress_region_stream(compressed_data, coded_box, box, out, device, blob):
+    """Region `box` of a stream with a full header that codes `coded_box`
+    (numpy axis order; None: the whole field) into `out` (None: a new
+    C-contiguous array, returned)."""
+    if compressed_data is None:
+        raise TypeError("compressed_data cannot be None")
+    ibuf, buf = _in_buffer(compressed_data)
+    field = _lib.zfp_field_alloc()
+    bstream = _lib.stream_open(buf, ibuf.size)
+    stream = _lib.zfp_stream_open(bstream)
+    try:
+        if device >= 0:
+            _lib.zfp_stream_set_hip_device(stream, device)
+        if _lib.zfp_read_header(stream, field, HEADER_FULL) == 0:
+            raise ValueError("Failed to read required zfp header")
+        fld = ctypes.cast(field, ctypes.POINTER(_Field)).contents
+        shape = tuple(n for n in (fld.nw, fld.nz, fld.ny, fld.nx) if n > 0)
+        if callable(box):
+            box = box(shape)
+        if out is None:
+            out = np.empty(tuple(e - f for f, e in box), dtype=ztype_to_dtype(fld.type))
+        coded = _chunk_of(list(reversed(coded_box))) if coded_box is not None else None
+        return _decompress_region_into(stream, field, coded, box, out, blob)
+    finally:
+        _lib.zfp_field_free(field)
+        _lib.zfp_stream_close(stream)
+        _lib.stream_close(bstream)
+
+
+def decompress_region(compressed_data, region, *, device=-1):
+    """The elements `region` of the array a stream with a full header codes
+    (compress_numpy's), as a new C-contiguous ndarray of the region's shape:
+    what decompress_numpy(compressed_data)[region] holds, decoding only the
+    blocks that intersect the region.  region: one slice per axis in numpy
+    order (step 1 or None, no negative indices); None or slice(None) is the
+    whole axis.  1D to 3D arrays."""
+    return _decompress_region_stream(compressed_data, None, lambda shape: _region_box(region, shape), None, device,
+                                     getattr(compressed_data, "block_index", None))
 
 
 def _decompress(compressed_data, ztype, shape, out=None, tolerance=-1, rate=-1, precision=-1, *, device=-1):
