@@ -8,7 +8,9 @@
  * `c2stats classes [zstep]`: the encoder's plane classes (code_planes_fr32 with
  * a PlaneClass, codec_dev.h) on every wave of the field (every zstep-th layer
  * of blocks): per plane the share of waves in class S, M and the wide form,
- * and the spread of both thresholds.
+ * the spread of the thresholds, kT included (class T: the planes of
+ * coefficients 0..3 from one table), and the class-T planes a wave codes in
+ * whole groups of three.
  * build: gcc -O2 -I../../oracle c2stats.c -lm -o /tmp/c2stats */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,14 +31,15 @@ static int bitlen_u32(uint32_t x)
 
 /* thresholds of planes_from_coeffs_auto<P3, true> (block3.h) from the widths of
  * a wave's coefficients in negabinary: ksw = bitlen(c32..63 | c31 >> 1) - 1,
- * kS = bitlen(c15..63) for a narrow wave (every c32..63 below 2^8), else 32 */
+ * kS = bitlen(c15..63) for a narrow wave (every c32..63 below 2^8), else 32;
+ * kT = bitlen(c4..63), at least kS */
 static int classes(int n, int zstep)
 {
-  long nw = 0, narrow = 0, cls[32][3] = {{0}}, hS[34] = {0}, hW[34] = {0};
+  long nw = 0, narrow = 0, cls[32][3] = {{0}}, hS[34] = {0}, hW[34] = {0}, hT[34] = {0}, hG[5] = {0};
   for (int bz = 0; bz < n / 4; bz += zstep)
     for (int by = 0; by < n / 4; by++)
       for (int bx0 = 0; bx0 < n / 4; bx0 += 64) {
-        uint32_t A = 0, B = 0, W = 0;
+        uint32_t A = 0, B = 0, W = 0, T = 0;
         for (int l = 0; l < 64; l++) {
           float v[64];
           for (int i = 0; i < 64; i++)
@@ -45,8 +48,10 @@ static int classes(int n, int zstep)
           int32_t q[64];
           oz_cast_fwd_f(q, v, 64, emax);
           oz_xform_f(q, 3, 0, 0);
-          for (int i = 15; i < 64; i++) {
+          for (int i = 4; i < 64; i++) {
             const uint32_t u = oz_to_nb_f(q[oz_perm3[i]]);
+            T |= u;
+            if (i < 15) continue;
             W |= u;
             if (i == 31) B = B | u;
             if (i >= 32) A |= u;
@@ -56,6 +61,12 @@ static int classes(int n, int zstep)
         const int ksw = bitlen_u32(A | (B >> 1)) - 1;
         int kS = nar ? bitlen_u32(W) : 32;
         if (kS <= ksw) kS = ksw + 1;
+        int kT = nar ? bitlen_u32(T) : 32;
+        if (kT < kS) kT = kS;
+        int groups = 0; /* whole groups 31..29, 28..26, 25..23, 22..20 at or above kT */
+        while (groups < 4 && 29 - 3 * groups >= kT) groups++;
+        hT[kT]++;
+        hG[groups]++;
         nw++;
         narrow += nar;
         hS[kS]++;
@@ -68,6 +79,10 @@ static int classes(int n, int zstep)
     printf("%5d  %6.2f  %6.2f  %6.2f\n", k, 100.0 * cls[k][0] / nw, 100.0 * cls[k][1] / nw, 100.0 * cls[k][2] / nw);
   printf("kS (waves):");
   for (int i = 0; i <= 32; i++) if (hS[i]) printf(" %d:%ld", i, hS[i]);
+  printf("\nkT (waves):");
+  for (int i = 0; i <= 32; i++) if (hT[i]) printf(" %d:%ld (%.1f %%)", i, hT[i], 100.0 * hT[i] / nw);
+  printf("\nclass-T groups of three planes (waves):");
+  for (int i = 0; i <= 4; i++) if (hG[i]) printf(" %d:%ld (%.1f %%)", i, hG[i], 100.0 * hG[i] / nw);
   printf("\nksw (waves):");
   for (int i = 0; i <= 32; i++) if (hW[i]) printf(" %d:%ld", i - 1, hW[i]);
   printf("\n");

@@ -104,14 +104,20 @@ __host__ __device__ inline bool no_partial_blocks3(const Geometry& g)
 // multiple of 64, `first` a multiple of 64 and wave-uniform): the row's
 // coordinates come from one division chain on the scalar unit, a lane adds its
 // x offset.  Same addresses as block_pos<true>(g, first + lane, 3).
-__device__ __forceinline__ BlockPos block_pos_row3(const Geometry& g, uint32_t first, uint32_t lane)
+// (row_origin3: the element offset of the wave's first block alone)
+__device__ __forceinline__ int64_t row_origin3(const Geometry& g, uint32_t first)
 {
   const uint32_t q0 = fastdiv(first, g.dv[0]);
   const uint32_t bx = first - q0 * g.nb[0];
   const uint32_t bz = fastdiv(q0, g.dv[1]);
   const uint32_t by = q0 - bz * g.nb[1];
-  const int64_t row = (int64_t)(g.f[0] + 4ull * bx) * g.s[0] + (int64_t)(g.f[1] + 4ull * by) * g.s[1] +
-                      (int64_t)(g.f[2] + 4ull * bz) * g.s[2];
+  return (int64_t)(g.f[0] + 4ull * bx) * g.s[0] + (int64_t)(g.f[1] + 4ull * by) * g.s[1] +
+         (int64_t)(g.f[2] + 4ull * bz) * g.s[2];
+}
+
+__device__ __forceinline__ BlockPos block_pos_row3(const Geometry& g, uint32_t first, uint32_t lane)
+{
+  const int64_t row = row_origin3(g, first);
   BlockPos p;
   p.off = row + (int64_t)(4u * lane) * g.s[0];
   p.cnt[0] = p.cnt[1] = p.cnt[2] = p.cnt[3] = 4;
@@ -220,6 +226,56 @@ __device__ __forceinline__ void gather3(S (&v)[64], const S* __restrict__ base, 
       for (int i = 0; i < 4; i++)
         pad_line(v, 4 * j + i, 16, cz);
   }
+}
+
+// Full-block gather of a wave whose 64 blocks lie in one x-row of unit x stride
+// (the case of block_pos_row3): `row` is the wave-uniform address of the row's
+// first value (row_origin3), so the 16 row bases row + j sy + k sz are formed on
+// the scalar unit and stay in scalar registers, and a lane adds one 32-bit byte
+// offset (16 bytes per lane for float): loads of the scalar-base +
+// vector-offset form, no per-lane 64-bit address.  Same addresses as gather3
+// at block_pos_row3.  (ZFP_ROW_SBASE=0: A/B builds without it)
+#ifndef ZFP_ROW_SBASE
+#define ZFP_ROW_SBASE 1
+#endif
+template <typename S>
+__device__ __forceinline__ void gather3_rows(S (&v)[64], const S* __restrict__ row, const Geometry& g, uint32_t lane)
+{
+  static_assert(sizeof(S) == 4, "one 16-byte load per row of the block");
+  const int64_t sy = g.s[1], sz = g.s[2];
+  const uint32_t lb = 16u * lane;
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint64_t a = reinterpret_cast<uint64_t>(row + j * sy + k * sz);
+#ifdef __HIP_DEVICE_COMPILE__
+      // the base as a scalar register pair, opaque: re-associated with the lane
+      // offset the sums are per-lane 64-bit adds again.  (The address is a
+      // global one: through the integer the compiler no longer sees that.)
+      asm("" : "+s"(a));
+      typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+      typedef const __attribute__((address_space(1))) u4* gptr;
+#if ZFP_NT_LOAD
+      const u4 x = __builtin_nontemporal_load(reinterpret_cast<gptr>(a + lb));
+#else
+      const u4 x = *reinterpret_cast<gptr>(a + lb);
+#endif
+      Vec16<S, 4> q;
+      __builtin_memcpy(&q, &x, 16);
+#else
+      const Vec16<S, 4> q = load16<S, 4>(reinterpret_cast<const S*>(a + lb));
+#endif
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        v[16 * k + 4 * j + i] = q.v[i];
+    }
+#ifdef __HIP_DEVICE_COMPILE__
+  // (keeps this body apart from the per-lane gather on the other side of the
+  // caller's branch: merged, the loads take a select of the two addresses, a
+  // 64-bit one per lane again)
+  asm volatile("; scalar row bases");
+#endif
 }
 
 template <typename S, bool VEC>
@@ -412,14 +468,26 @@ __device__ __forceinline__ PlaneClass planes_from_coeffs_auto(uint32_t (&Pl)[32]
       const uint32_t b = ((uint32_t)q[P3 ? kPerm3[31] : 31] + 0xaaaaaaaau) ^ 0xaaaaaaaau;
       pc.ksw = (int)nbits32(wave_or(a | (b >> 1))) - 1;
       pc.kS = 0;
+      // kT on the way: planes are compared with 0xf until some lane has a bit
+      // of coefficients 4..31, and from that plane on with 0x7fff
+      int kT = 0;
+      bool tiny = ZFP_PLANE_TINY != 0;
 #pragma unroll
       for (int k = 31; k >= 0; k--) {
+        if (tiny) {
+          if (__builtin_amdgcn_ballot_w64(Pl[k] > 0xfu) == 0)
+            continue;
+          kT = k + 1;
+          tiny = false;
+        }
         if (__builtin_amdgcn_ballot_w64(Pl[k] > 0x7fffu) != 0) {
           pc.kS = k + 1;
           break;
         }
       }
       pc.kS = pc.kS > pc.ksw ? pc.kS : pc.ksw + 1;
+      if (ZFP_PLANE_TINY)
+        pc.kT = kT > pc.kS ? kT : pc.kS;
     }
     planes_high_narrow<P3>(Ph, q);
   } else {
@@ -633,6 +701,11 @@ __device__ __forceinline__ uint32_t decode_ints3(WordReader& r, const uint32_t* 
 // wave-uniform, taken only if some lane needs it, and re-reads the block
 // through `reload` so the inputs are dead after the fast cast (the cast is
 // done in place, keeping the register footprint at one block).
+// ZFP_CAST_FORM: the scale multiply of the fast cast (1: packed pairs as loaded;
+// 0: left to the compiler, A/B builds).
+#ifndef ZFP_CAST_FORM
+#define ZFP_CAST_FORM 1
+#endif
 template <typename Reload>
 __device__ __forceinline__ int lossy_emax_cast(int32_t (&q)[64], float (&v)[64], const CodecParams& cp,
                                                uint32_t& mp, Reload&& reload)
@@ -653,9 +726,24 @@ __device__ __forceinline__ int lossy_emax_cast(int32_t (&q)[64], float (&v)[64],
   mp = precision3(emax, cp);
   const bool cast = mp != 0 && emax != -127;
   const float s = __uint_as_float((uint32_t)(157 - emax) << 23);
+#if ZFP_CAST_FORM == 1 && defined(__HIP_DEVICE_COMPILE__)
+  // the pairs as loaded (each 16-byte load is two aligned register pairs): one
+  // v_pk_mul_f32 per pair and no register moves.  Left to itself the SLP
+  // vectoriser pairs values of different loads and moves them together (48
+  // v_mov_b32 in the rate-16 kernel).
+  typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int i = 0; i < 64; i += 2) {
+    f2 p = {v[i], v[i + 1]};
+    p *= s;
+    q[i] = (int32_t)p.x;
+    q[i + 1] = (int32_t)p.y;
+  }
+#else
 #pragma unroll
   for (int i = 0; i < 64; i++)
     q[i] = (int32_t)(s * v[i]);
+#endif
   if (__any(cast && (bad || emax < -97))) {
     float w[64];
     reload(w);

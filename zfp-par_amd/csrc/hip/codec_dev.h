@@ -207,11 +207,37 @@ __device__ __forceinline__ uint32_t dbl16(const uint32_t* lut, uint32_t u)
 //             plane's group bits with the leading "1" test, and in its low five
 //             bits the shift that places the second byte's expansion after it
 //             (code_planes_fr32).
+//   tiny[(4 - n) * 16 + p] = v | len << 16: a whole plane whose bits p < 16 lie
+//             in coefficients 0..3 with n <= 4 of them significant (class T of
+//             code_planes_fr32): v = (p & mask(n)) | g << n, the n verbatim bits
+//             and the group bits g = (dbl(xs) << 1 | 1) - 2^e1 of xs = p >> n,
+//             e1 = bitlen(xs) + popcount(xs); len = n + e1 + 1 <= 9.  Rows run
+//             from n = 4 down to n = 0: the coder keeps 32 - n.
+constexpr int kTinyEntries = 80;
 struct CoderTables {
   uint32_t dbl[256];
   uint32_t lead[256];
-  constexpr CoderTables() : dbl(), lead()
+  uint32_t tiny[kTinyEntries];
+  constexpr CoderTables() : dbl(), lead(), tiny()
   {
+    for (uint32_t n = 0; n <= 4; n++)
+      for (uint32_t p = 0; p < 16; p++) {
+        const uint32_t xs = p >> n;
+        uint32_t d = 0, q = 0, c = 0, bl = 0;
+        for (int i = 0; i < 4; i++) {
+          if ((xs >> i) & 1u) {
+            d |= 3u << q;
+            q += 2;
+            c++;
+            bl = (uint32_t)i + 1u;
+          } else {
+            q += 1;
+          }
+        }
+        const uint32_t e1 = bl + c;
+        const uint32_t g = ((d << 1) | 1u) - (1u << e1);
+        tiny[(4u - n) * 16u + p] = (p & ((1u << n) - 1u)) | (g << n) | ((n + e1 + 1u) << 16);
+      }
     for (uint32_t b = 0; b < 256; b++) {
       uint32_t d = 0, p = 0, c = 0;
       for (int i = 0; i < 8; i++) {
@@ -1008,18 +1034,49 @@ __device__ __forceinline__ void code_planes_fru(OrSlot& os, const uint32_t* lut,
 //                  value, written once;
 //   kS > k > ksw   class M: the 32-bit body without its leave test;
 //   k <= ksw       code_planes_fru from plane ksw on.
-// Either threshold may be larger than needed (kS > ksw always): the later
+//   k >= kT        class T (ZFP_PLANE_TINY=0: A/B builds without it): no lane
+//                  has a bit of coefficients 4..63 in this plane or above, so
+//                  n' <= 4 and the plane's at most 9 bits and its length are one
+//                  entry of CoderTables::tiny, read at (n, Pl[k]); n' needs no
+//                  table (two VALU on 32 - n), so the reads of a group do not
+//                  wait for each other.  The planes 31..20 are taken in fixed
+//                  groups of three (at most 27 bits): a group whose lowest plane
+//                  is >= kT is accumulated in registers and written once, with
+//                  one position update and one clamp -- the group starts at or
+//                  before the budget end, so what it puts past it falls into
+//                  the slot's spare dwords as any write there does, and every
+//                  bit below the budget end sits where the per-plane clamp puts
+//                  it.  A group that straddles kT is coded by class S.
+// Any threshold may be larger than needed (kT >= kS > ksw always): the later
 // forms are general.
 #ifndef ZFP_PLANE_CLASS
 #define ZFP_PLANE_CLASS 1
 #endif
+#ifndef ZFP_PLANE_TINY
+#define ZFP_PLANE_TINY 1
+#endif
 constexpr int kPlanesTested = -2;  // PlaneClass::ksw of a wave without classes
+constexpr int kTinyLowest = 20;    // class T groups: 31..29, 28..26, 25..23, 22..20
 struct PlaneClass {
-  int ksw;  // -1 .. 31: the first plane of the wide form (-1: none); or kPlanesTested
-  int kS;   // 0 .. 32: planes kS .. 31 are class S
+  int ksw;      // -1 .. 31: the first plane of the wide form (-1: none); or kPlanesTested
+  int kS;       // 0 .. 32: planes kS .. 31 are class S
+  int kT = 32;  // kS .. 32: planes kT .. 31 are class T (32: none)
 };
 
 __device__ __forceinline__ uint32_t nbits32(uint32_t x) { return 32u - (uint32_t)__clz((int)x); }
+
+// leading zeros of x, ~0u for x == 0 (v_ffbh_u32 as it is: an unsigned minimum
+// with it leaves 32 - n alone on an empty plane)
+__device__ __forceinline__ uint32_t ffbh_or_ones(uint32_t x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+  uint32_t r;
+  asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+#else
+  return x ? (uint32_t)__builtin_clz(x) : ~0u;
+#endif
+}
 
 // OR over the wave, every lane active; the result is wave-uniform (an SGPR):
 // four row shifts, two row broadcasts, one v_readlane.  (Host emulation: a
@@ -1059,12 +1116,7 @@ __device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, 
   // (no exit from the loops: left at a wave-uniform plane they have no constant
   // trip count and are not unrolled.  The planes past ksw are skipped four at a
   // time; a wave that is wide from the first plane on goes straight on.)
-#pragma unroll
-  for (int k4 = 28; k4 >= 0; k4 -= 4) {
-    if (ksw >= k4 + 3)
-      continue;
-#pragma unroll
-    for (int k = k4 + 3; k >= k4; k--) {
+  auto plane = [&](const int k) __attribute__((always_inline)) {
       if (k >= kS) {
         exp_vpad();
         const uint32_t pl = Pl[k];
@@ -1107,7 +1159,48 @@ __device__ __forceinline__ void code_planes_fr32(uint32_t* slot, uint32_t jmax, 
         Q = Qn > Qlim ? Qn : Qlim;
         n += bl;
       }
+  };
+  // planes 31..kTinyLowest in groups of three: class T, or plane by plane
+#if ZFP_PLANE_TINY
+  const int kT = pc.kT;
+  const uint32_t ttiny = tdbl + 2048u - 28u * 64u;  // row 32 - n - 28 of CoderTables::tiny
+#endif
+#pragma unroll
+  for (int hi = 31; hi >= kTinyLowest + 2; hi -= 3) {
+    if (ksw >= hi)
+      continue;
+#if ZFP_PLANE_TINY
+    if (hi - 2 >= kT) {
+      exp_vpad();
+      uint32_t r = hi == 31 ? 32u : 32u - n;  // 32 - n
+      uint32_t acc = 0, off = 0;
+#pragma unroll
+      for (int k = hi; k >= hi - 2; k--) {
+        const uint32_t pl = Pl[k];
+        const uint32_t e = *lds_at(ttiny + (r << 6) + (pl << 2));
+        acc = k == hi ? e & 0xffffu : acc | ((e & 0xffffu) << off);
+        off = k == hi ? e >> 16 : off + (e >> 16);
+        const uint32_t z = ffbh_or_ones(pl);
+        r = r < z ? r : z;
+      }
+      fr_write32(Q, acc);
+      const int32_t Qn = Q - (int32_t)off;
+      Q = Qn > Qlim ? Qn : Qlim;
+      n = 32u - r;
+      continue;
     }
+#endif
+#pragma unroll
+    for (int k = hi; k >= hi - 2; k--)
+      plane(k);
+  }
+#pragma unroll
+  for (int k4 = kTinyLowest - 4; k4 >= 0; k4 -= 4) {
+    if (ksw >= k4 + 3)
+      continue;
+#pragma unroll
+    for (int k = k4 + 3; k >= k4; k--)
+      plane(k);
   }
   if (ksw >= 0) {
 #if ZFP_FRU

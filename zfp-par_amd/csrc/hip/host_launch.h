@@ -356,7 +356,7 @@ static int launch_encode(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_ou
     auto magic_of = [](uint32_t d) { return d > 1 ? (uint32_t)((0x100000000ull + d - 1) / d) : 0u; };
     const uint32_t magic_w = magic_of(sw), magic_c = (sw & 1) ? 0u : magic_of(sw / 2);
     size_t lds = (size_t)kWavesPerGroup * 64 * sdw * 4;
-    if (lds + 2 * kLutBytes > 160 * 1024)
+    if (lds + sizeof(CoderTables) > 160 * 1024)  // the aligned kernels' static LDS: the coder tables
       return fail("zfp_hip: block size %u bits too large for LDS", p.cp.maxbits);
     Partial* parts = nullptr;
     if (g0) {

@@ -246,8 +246,23 @@ __global__ __launch_bounds__(64 * WPG, 3) void encode3_aligned(const S* __restri
 template <int SW>
 constexpr uint32_t kAlignedSlotDwords = slot_dwords_for(64u * SW) | 1u;
 
+// ZFP_FULL_WAVES (3: A/B builds with the bound of the other instantiations): the
+// NOPART kernels are compiled for four waves per SIMD, at most 128 VGPRs.  With
+// the scalar row bases and the pairwise cast the allocator took 129 under the
+// looser bound; under this one the rate-16 kernel has 118 and the run-time-stride
+// one 116, as before, and neither has scratch.
+// ZFP_TABLES_FIRST=0: A/B builds that copy the coder tables after the block
+// loads, as before.  The early request and the tiny[] table
+// are the NOPART float kernels' alone (kTab below): the other instantiations,
+// the f64 ones at their register bound among them, compile as they did.
+#ifndef ZFP_TABLES_FIRST
+#define ZFP_TABLES_FIRST 1
+#endif
+#ifndef ZFP_FULL_WAVES
+#define ZFP_FULL_WAVES 4
+#endif
 template <typename S, bool VEC, bool NOPART = false, int SW = 0>
-__global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restrict__ data, Geometry g, CodecParams cp,
+__global__ __launch_bounds__(256, NOPART ? ZFP_FULL_WAVES : 3) void encode3_aligned_full(const S* __restrict__ data, Geometry g, CodecParams cp,
                                                             uint64_t* __restrict__ out, uint32_t sw_, uint32_t sdw_,
                                                             uint32_t magic_c)
 {
@@ -255,7 +270,8 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
   static_assert(SW == 0 || (SW % 2 == 0 && kHw <= 64 && (kHw & (kHw - 1)) == 0), "SW: 2 hw, hw a power of two");
   const uint32_t sw = SW ? (uint32_t)SW : sw_;
   const uint32_t sdw = SW ? kAlignedSlotDwords<SW> : sdw_;
-  __shared__ uint32_t lut[512];  // CoderTables: dbl[256], lead[256]
+  constexpr bool kTab = NOPART && sizeof(S) == 4;  // the kernels whose coder reads tiny[]
+  __shared__ uint32_t lut[512 + (kTab ? kTinyEntries : 0)];  // CoderTables: dbl[256], lead[256](, tiny[80])
   extern __shared__ uint32_t ldsw[];
   const int lane = threadIdx.x & 63;
   const int wv = NOPART ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
@@ -265,18 +281,51 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
   const uint64_t b = first + lane;
   S v[64];
   __builtin_amdgcn_s_setprio(1);
-  BlockPos p;
-  if (NOPART && (g.nb[0] & 63u) == 0)
+  // the coder tables are requested ahead of the block: loads return in order, so
+  // behind the 16 block loads their copy to LDS waits for the whole block, and
+  // the slot zero-fill behind it
+  constexpr bool kTabFirst = kTab && ZFP_TABLES_FIRST;
+  const uint4* tsrc = reinterpret_cast<const uint4*>(&kCoderTables);
+  // (tiny[]: 20 quads; the other lanes copy the last one again, so the load goes
+  // out with the two others and not behind a branch and their wait)
+  const int tq = 128 + (lane < kTinyEntries / 4 ? lane : kTinyEntries / 4 - 1);
+  uint4 t0{}, t1{}, t2{};
+  if constexpr (kTabFirst) {
+    t0 = tsrc[lane];
+    t1 = tsrc[lane + 64];
+    t2 = tsrc[tq];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  BlockPos p{};
+  // a wave inside one x-row (wave-uniform): scalar row bases, one 32-bit lane offset
+  constexpr bool kRows = NOPART && VEC && sizeof(S) == 4 && ZFP_ROW_SBASE;
+  const bool rows = NOPART && __builtin_expect((g.nb[0] & 63u) == 0, 1);
+  const S* row = data;
+  auto gather = [&](S (&r)[64]) __attribute__((always_inline)) {
+    if constexpr (kRows) {
+      if (rows) {
+        gather3_rows<S>(r, row, g, (uint32_t)lane);
+        return;
+      }
+    }
+    gather3<S, VEC, NOPART>(r, data, g, p);
+  };
+  if (kRows && rows)
+    row = data + row_origin3(g, (uint32_t)first);
+  else if (rows)
     p = block_pos_row3(g, (uint32_t)first, (uint32_t)lane);
   else
     p = block_pos<NOPART>(g, b, 3);
-  gather3<S, VEC, NOPART>(v, data, g, p);
+  gather(v);
   __builtin_amdgcn_s_setprio(0);
   {
-    const uint4* src = reinterpret_cast<const uint4*>(&kCoderTables);
     uint4* dst = reinterpret_cast<uint4*>(lut);
-    dst[lane] = src[lane];
-    dst[lane + 64] = src[lane + 64];
+    if constexpr (!kTabFirst) {
+      dst[lane] = tsrc[lane];
+      dst[lane + 64] = tsrc[lane + 64];
+      if constexpr (kTab)
+        dst[tq] = tsrc[tq];
+    }
     uint4* z = reinterpret_cast<uint4*>(wslot);
     if constexpr (SW != 0) {
       constexpr uint32_t kQuads = 16 * kAlignedSlotDwords<SW>;  // of the wave's 64 slots
@@ -289,13 +338,18 @@ __global__ __launch_bounds__(256, 3) void encode3_aligned_full(const S* __restri
       for (uint32_t i = lane; i < 16 * sdw; i += 64)
         z[i] = make_uint4(0, 0, 0, 0);
     }
+    if constexpr (kTabFirst) {
+      __builtin_amdgcn_sched_barrier(0);
+      dst[lane] = t0;
+      dst[lane + 64] = t1;
+      dst[tq] = t2;
+    }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) only
     __builtin_amdgcn_wave_barrier();
   }
   OrSlot os{reinterpret_cast<uint64_t*>(wslot + (size_t)lane * sdw), sdw - 1};
   // (whole waves: the builder may class the planes for the coder)
-  encode_block3<S, false, true, false, NOPART ? 1 + ZFP_PLANE_CLASS : 0>(
-    os, lut, v, cp, [&](S (&r)[64]) { gather3<S, VEC, NOPART>(r, data, g, p); });
+  encode_block3<S, false, true, false, NOPART ? 1 + ZFP_PLANE_CLASS : 0>(os, lut, v, cp, gather);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   uint64_t* dst = out + first * sw;
