@@ -304,6 +304,18 @@ size_t zfp_decompress_chunk(zfp_stream* stream, const zfp_chunk* chunk, zfp_fiel
  * decoded; 1D to 3D fields.  zfp_true on success. */
 zfp_bool zfp_decompress_region(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
                                const zfp_chunk* region, zfp_field* out);
+/* MI355X addition: region encode, the write twin of zfp_decompress_region.
+ * Rewrite region [f,e) of `region` in the fixed-rate stream that codes `coded` (NULL: the whole field) of
+ * `field` (type, extents; its data pointer is not used) from `in`, a field of the region's extents with its own
+ * pointer and strides, in place: every block that intersects the region is coded again (a block the region
+ * only cuts through is decoded, overlaid and coded again; the elements it keeps go through one more lossy
+ * round), every other bit of the stream stays.  The stream must be positioned for writing at the first block
+ * (stream_wseek after any header, or right after zfp_write_header); its position (stream_wtell) is left
+ * unchanged and bits pending in the bitstream's buffer are kept.  zfp_false, with nothing written, for a
+ * variable-rate stream and for a type, extent or dimensionality mismatch between `in` and the region;
+ * 1D to 3D fields. */
+zfp_bool zfp_compress_region(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
+                             const zfp_chunk* region, const zfp_field* in);
 /* zfp.h:797-838: dispatch with an explicit execution policy, strided flag,
  * dimensionality and scalar type (zfp_compress_chunk derives them) */
 size_t zfp_compress_call(zfp_stream* stream, const zfp_chunk* chunk, const zfp_field* field, const uint exec,

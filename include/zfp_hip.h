@@ -124,6 +124,42 @@ int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], cons
                               int device, const zfp_hip_index* index, uint64_t* blocks_read);
 
 /*
+ * Region encode: rewrite the sub-box [lo, hi) (element granular, f <= lo < hi
+ * <= e per axis) of the fixed-rate stream that codes the chunk box of `job`,
+ * in place.  `src` (host or device memory) holds element x of the region at
+ * src[sum over axes of (x - lo) * src_stride] (element strides; job->s is not
+ * used).  After the call every block that intersects the region holds exactly
+ * the bits zfp_hip_compress would write for it from the image: the field as a
+ * full decode of the old stream gives it, with the region's elements replaced
+ * by the source.  A block whose elements inside the field all lie in the
+ * region is coded from the source alone and its old bits are never read; a
+ * block the region cuts through (or one at a chunk end that is neither a
+ * multiple of 4 from the chunk's origin nor the field's edge) is decoded,
+ * overlaid and coded again, so the elements it keeps go through one more lossy
+ * round.  Every other bit of the stream is left as it was: blocks that do not
+ * intersect the region, bits below `bit_offset`, bits past the last block,
+ * words past the stream.
+ * 1D to 3D, fixed rate only (in a variable-rate stream a block of another
+ * length would move every later block).  A null pointer, an empty region or
+ * one outside the coded box, a 4D job, a variable-rate job, more than
+ * 2^32 - 1 region blocks and a stream whose `capacity_words` ends before the
+ * last needed block's last bit return 0 before any GPU call, with the stream
+ * untouched.
+ * Host `words`: the words from the first needed block's first word to the
+ * last needed block's last word are copied to the device, merged there and
+ * copied back; for a thin region across a large stream (an x slice) that span
+ * is nearly the whole stream -- streams in device memory are the fast path.
+ * Two calls on one stream at the same time are not supported.
+ * *blocks_written (optional) receives the number of blocks coded: the product
+ * formula of zfp_hip_decompress_region's blocks_read.
+ * zfp_hip_last_timing reports the region kernel as it does any encode.
+ */
+int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4],
+                            const void* src, const int64_t src_stride[4],
+                            uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
+                            int device, uint64_t* blocks_written);
+
+/*
  * Build the block index of the variable-rate stream at `words` for the chunk
  * box of `job`, blocks starting at bit `bit_offset` (a parallel parse of the
  * stream on the GPU; see scan.h).  Returns 0 for fixed-rate jobs, truncated

@@ -10,9 +10,9 @@
 // Everything that is checked before any GPU call: pointers, the job, the
 // region against the coded box, the dimensionality and the block count.
 static int plan_region(const zfp_hip_job* job, const uint64_t* lo, const uint64_t* hi, const void* dst,
-                       const int64_t* dst_stride, const uint64_t* words, Plan& p, RegionGeom& rg)
+                       const int64_t* dst_stride, const uint64_t* words, Plan& p, RegionGeom& rg,
+                       const char* who = "zfp_hip_decompress_region", const char* what = "decode")
 {
-  const char* who = "zfp_hip_decompress_region";
   if (!job || !lo || !hi || !dst || !dst_stride || !words)
     return fail("%s: null job, region, destination, stride or stream pointer", who);
   zfp_hip_job j = *job;  // (job->s is not used: the destination has its own strides)
@@ -26,7 +26,7 @@ static int plan_region(const zfp_hip_job* job, const uint64_t* lo, const uint64_
                   (unsigned long long)lo[a], (unsigned long long)hi[a], a, (unsigned long long)j.f[a],
                   (unsigned long long)j.e[a]);
   if (p.dims == 4)
-    return fail("%s: 4D region decode is not supported (1D to 3D fields only)", who);
+    return fail("%s: 4D region %s is not supported (1D to 3D fields only)", who, what);
   rg = make_region_geom(p.g, p.dims, lo, hi, dst_stride);
   if (rg.nrblocks > 0xffffffffull)  // (three factors below 2^32 whose product divides the box's block count)
     return fail("%s: %llu region blocks in one call (at most 2^32 - 1)", who, (unsigned long long)rg.nrblocks);

@@ -26,6 +26,7 @@
 #include "host_scan.h"         // index scan of a stream without an index
 #include "host_pipeline.h"     // host <-> device box copies, the slab pipeline
 #include "host_region.h"       // region decode: validation, start table, launch, copy-out
+#include "host_region_enc.h"   // region encode: validation, source image, launch, copy-back
 
 // ---------------------------------------------------------------------------
 // How every entry point that uses the device begins: the job's plan, the
@@ -355,6 +356,28 @@ int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], cons
   }
   if (ok && blocks_read)
     *blocks_read = rg.nrblocks;
+  return lease.done(ok);
+}
+
+int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4], const void* src,
+                            const int64_t src_stride[4], uint64_t* words, uint64_t capacity_words,
+                            uint64_t bit_offset, int device, uint64_t* blocks_written)
+{
+  // (as zfp_hip_decompress_region: everything is validated before the first GPU call)
+  Plan p;
+  RegionGeom rg;
+  if (!plan_region_enc(job, lo, hi, src, src_stride, words, capacity_words, bit_offset, p, rg))
+    return 0;
+  if (zfp_hip_device_count() <= 0)
+    return fail("zfp_hip_compress_region: no HIP device available");
+  CtxLease lease;
+  lease.c = acquire_ctx(device);
+  if (!lease.c)
+    return 0;
+  t_timing = Timing{};
+  const int ok = region_enc_once(lease.c, p, rg, src, src_stride, words, capacity_words, bit_offset);
+  if (ok && blocks_written)
+    *blocks_written = rg.nrblocks;
   return lease.done(ok);
 }
 

@@ -1217,6 +1217,76 @@ zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zf
   return zfp_true;
 }
 
+/* Region encode (no reference equivalent): the blocks of `coded` that intersect
+ * `region`, coded again from `in` in place -- zfp_hip_compress_region with the
+ * stream's device and its write position (stream_wtell), which stays where it
+ * is.  Fixed rate only.  The bits pending in the bitstream's buffer (the part
+ * of the first block's word below the write position) are not lost: the device
+ * leaves the stream's bits below the position as they are, and after the call
+ * the pending bits are stored into that word, so that the stream's memory is
+ * complete while the buffer still holds them. */
+zfp_bool zfp_compress_region(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
+                             const zfp_chunk* region, const zfp_field* in)
+{
+  bitstream* s;
+  zfp_hip_job job;
+  zfp_chunk whole;
+  ptrdiff_t st[4];
+  uint64 lo[4], hi[4];
+  int64_t ss[4];
+  uint d;
+  if (!zfp || !zfp->stream || !field || !region || !in || !in->data)
+    return zfp_false;
+  s = zfp->stream;
+  d = zfp_field_dimensionality(field);
+  if (field->type != in->type || zfp_field_dimensionality(in) != d)
+    return zfp_false;
+  if (variable_rate(zfp, field))
+    return zfp_false;
+  if (!coded) {
+    whole.fx = whole.fy = whole.fz = whole.fw = 0;
+    whole.ex = field->nx;
+    whole.ey = field->ny;
+    whole.ez = field->nz;
+    whole.ew = field->nw;
+    coded = &whole;
+  }
+  {
+    const size_t f[4] = {region->fx, region->fy, region->fz, region->fw};
+    const size_t e[4] = {region->ex, region->ey, region->ez, region->ew};
+    const size_t n[4] = {in->nx, in->ny, in->nz, in->nw};
+    field_strides(in, st);
+    for (uint a = 0; a < 4; a++) {
+      lo[a] = a < d ? f[a] : 0;
+      hi[a] = a < d ? e[a] : 0;
+      ss[a] = a < d ? (int64_t)st[a] : 0;
+      if (a < d && (e[a] <= f[a] || e[a] - f[a] != n[a]))
+        return zfp_false;
+    }
+  }
+  job_from(&job, zfp, coded, field);
+  if (!zfp_hip_compress_region(&job, lo, hi, in->data, ss, s->begin, (uint64)(s->end - s->begin), stream_wtell(s),
+                               stream_device(zfp), NULL)) {
+    report("zfp_compress_region");
+    return zfp_false;
+  }
+  if (s->bits) {
+    /* the pending bits into the word they belong to (s->ptr stays) */
+    const uint64 m = ((uint64)1 << s->bits) - 1;
+    uint64 w = 0;
+    if (s->device) {
+      if (!zfp_hip_memcpy(&w, s->ptr, sizeof w))
+        return zfp_false;
+      w = (w & ~m) | (s->buffer & m);
+      if (!zfp_hip_memcpy(s->ptr, &w, sizeof w))
+        return zfp_false;
+    } else {
+      *s->ptr = (*s->ptr & ~m) | (s->buffer & m);
+    }
+  }
+  return zfp_true;
+}
+
 /* One block of the low-level API (encode.c / decode.c templates: zfp_encode_
  * block_*, zfp_decode_block_*): the same GPU call as a chunk, on a field that
  * is the block, at the stream's bit position -- pending bits of a partly

@@ -21,8 +21,8 @@ from multiprocessing.sharedctypes import RawArray
 
 import numpy as np
 
-from .zfpy_c import (_compress_portion, _decompress_portion, _decompress_region_stream, _region_box, device_count,
-                     zfp_chunkit)
+from .zfpy_c import (_compress_portion, _compress_region_bytes, _decompress_portion, _decompress_region_stream,
+                     _fixed_rate, _region_box, device_count, zfp_chunkit)
 
 _TYPECODE = {"float32": "f", "float64": "d", "int32": "i", "int64": "q"}
 _ITEMSIZE = {"float32": 4, "float64": 8, "int32": 4, "int64": 8}
@@ -62,6 +62,7 @@ class zfp_p:
         self._chunkit = zfp_chunkit(self._np_array, chunks_per_block, method)
         self._compress_data = []
         self._index_of = []  # (stream object, block-index blob) per chunk of the last compress()
+        self._fixed = False  # the last compress() was fixed rate (compress_region)
         ndev = device_count()
         self._ngpus = max(1, min(ngpus or 1, ndev if ndev > 0 else 1))
 
@@ -91,6 +92,7 @@ class zfp_p:
         # until the new ones are assigned.  So a compress() that raises leaves
         # the object without compressed data (decompress() then raises too).
         self._compress_data, self._index_of = [], []
+        self._fixed = _fixed_rate(tolerance, rate)
         tasks = [(i, tolerance, rate, precision) for i in range(self._chunkit.get_nchunks())]
 
         def one(i, tol, r, p):
@@ -151,6 +153,51 @@ class zfp_p:
         with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
             pool.starmap(one, tasks)
         return out
+
+    def compress_region(self, region, values=None, nthreads=-1):
+        """Code the elements `region` again, from `values` (an ndarray of the region's shape and the
+        array's dtype; None: the shared array's own elements of the region), into the chunk streams the
+        last fixed-rate compress() kept, without coding anything else: only the blocks that intersect
+        the region are written.  Every chunk whose box intersects the region gets a new bytes object
+        (the old stream with the region's blocks replaced), made on the thread pool, one chunk per
+        task; the other chunks keep their stream objects.  Returns the list of chunk streams.
+        Raises after a variable-rate compress() and when there is no compressed data."""
+        if nthreads == -1:
+            nthreads = cpu_count()
+        data = self._compress_data
+        ck = self._chunkit
+        if len(data) != ck.get_nchunks():
+            raise RuntimeError("no compressed data for this partition (call compress first)")
+        if not self._fixed:
+            raise RuntimeError("compress_region needs fixed-rate chunk streams (compress(rate=...)): in a "
+                               "variable-rate stream a block of another length moves every later block")
+        nd = ck.ndim
+        box = _region_box(region, tuple(ck.ns_python))
+        if values is None:
+            values = self._np_array[tuple(slice(f, e) for f, e in box)]
+        if not isinstance(values, np.ndarray):
+            raise TypeError("values must be a numpy array")
+        if values.dtype != np.dtype(ck.dtype):
+            raise TypeError("values of dtype %s, the array holds %s" % (values.dtype, np.dtype(ck.dtype)))
+        if values.shape != tuple(e - f for f, e in box):
+            raise ValueError("values of shape %s, the region has shape %s"
+                             % (values.shape, tuple(e - f for f, e in box)))
+        tasks = []
+        for i in range(len(data)):
+            coded = list(reversed(ck.boxes[i][:nd]))  # numpy axis order
+            part = [(max(f, cf), min(e, ce)) for (f, e), (cf, ce) in zip(box, coded)]
+            if all(f < e for f, e in part):
+                tasks.append((i, coded, part))
+
+        def one(i, coded, part):
+            view = values[tuple(slice(f - f0, e - f0) for (f, e), (f0, _) in zip(part, box))]
+            return i, _compress_region_bytes(data[i], coded, part, view, self._device_of(i))
+
+        with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
+            res = pool.starmap(one, tasks)
+        for i, new in res:  # (all tasks succeeded: a failure leaves every stream as it was)
+            data[i] = new
+        return data
 
 
 def write_json_header(filename, dimensions, block_splits, compressed_files):

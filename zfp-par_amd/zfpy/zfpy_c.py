@@ -61,6 +61,8 @@ for _name, _res, _args in [
     ("zfp_compress", _sz, [_vp, _vp]), ("zfp_decompress", _sz, [_vp, _vp]),
     ("zfp_compress_chunk", _sz, [_vp, _vp, _vp]), ("zfp_decompress_chunk", _sz, [_vp, _vp, _vp]),
     ("zfp_decompress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
+    ("zfp_compress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
+    ("stream_rtell", _u64, [_vp]), ("stream_wseek", None, [_vp, _u64]),
     ("zfp_write_header", _sz, [_vp, _vp, _u32]), ("zfp_read_header", _sz, [_vp, _vp, _u32]),
     ("zfp_optimal_parts_from_size", _vp, [_i32, _vp, ctypes.c_float, _i32]),
     ("zfp_chunks_from_blocks", _vp, [_i32, _vp, _vp]), ("zfp_blocks_free", None, [_vp]),
@@ -553,6 +555,100 @@ def decompress_region(compressed_data, region, *, device=-1):
     whole axis.  1D to 3D arrays."""
     return _decompress_region_stream(compressed_data, None, lambda shape: _region_box(region, shape), None, device,
                                      getattr(compressed_data, "block_index", None))
+
+
+_ZFP_MIN_EXP = -1074
+
+
+def _compress_region_at(addr, nbytes, coded_box, box, values, device):
+    """zfp_compress_region on the stream with a full header in the `nbytes`
+    writable bytes at `addr` (a whole number of 64-bit words), in place.
+    coded_box, box: [(first, end)] per numpy axis (coded_box None: the whole
+    field; box may be a function of the stream's shape); values: ndarray of the
+    box's shape and the stream's dtype.  Returns the number of blocks coded."""
+    field = _lib.zfp_field_alloc()
+    bstream = _lib.stream_open(addr, nbytes)
+    stream = _lib.zfp_stream_open(bstream)
+    try:
+        if device >= 0:
+            _lib.zfp_stream_set_hip_device(stream, device)
+        if _lib.zfp_read_header(stream, field, HEADER_FULL) == 0:
+            raise ValueError("Failed to read required zfp header")
+        fld = ctypes.cast(field, ctypes.POINTER(_Field)).contents
+        shape = tuple(n for n in (fld.nw, fld.nz, fld.ny, fld.nx) if n > 0)
+        mb, xb, mp, me = _u32(), _u32(), _u32(), _i32()
+        _lib.zfp_stream_params(stream, ctypes.byref(mb), ctypes.byref(xb), ctypes.byref(mp), ctypes.byref(me))
+        if mb.value != xb.value or me.value < _ZFP_MIN_EXP:
+            raise ValueError("compress_region needs a fixed-rate stream (in a variable-rate stream a block of "
+                             "another length moves every later block)")
+        if callable(box):
+            box = box(shape)
+        dtype = np.dtype(ztype_to_dtype(fld.type))
+        if not isinstance(values, np.ndarray):
+            raise TypeError("values must be a numpy array")
+        if values.dtype != dtype:
+            raise TypeError("values of dtype %s, the stream holds %s" % (values.dtype, dtype))
+        want = tuple(e - f for f, e in box)
+        if values.shape != want:
+            raise ValueError("values of shape %s, the region has shape %s" % (values.shape, want))
+        coded = coded_box if coded_box is not None else [(0, n) for n in shape]
+        nblocks = 1
+        for (f, e), (cf, _) in zip(box, coded):
+            nblocks *= (e - 1 - cf) // 4 - (f - cf) // 4 + 1
+        # the header was read: the same position, for writing
+        _lib.stream_wseek(bstream, _lib.stream_rtell(bstream))
+        ck = _chunk_of(list(reversed(box)))
+        cck = _chunk_of(list(reversed(coded_box))) if coded_box is not None else None
+        ifield = _make_field(values.ctypes.data, fld.type, list(reversed(values.shape)),
+                             [s // values.itemsize for s in reversed(values.strides)])
+        try:
+            ret = _lib.zfp_compress_region(stream, field, ctypes.byref(cck) if cck is not None else None,
+                                           ctypes.byref(ck), ifield)
+        finally:
+            _lib.zfp_field_free(ifield)
+        if not ret:
+            raise RuntimeError("error during zfp region compression")
+        return nblocks
+    finally:
+        _lib.zfp_field_free(field)
+        _lib.zfp_stream_close(stream)
+        _lib.stream_close(bstream)
+
+
+def compress_region(stream, region, values, *, device=-1):
+    """Rewrite the elements `region` of the array that a fixed-rate stream with
+    a full header codes (compress_numpy's with rate=) from `values`, in place.
+    stream: a writable buffer (bytearray, writable memoryview, uint8 ndarray), a
+    whole number of 64-bit words long; bytes and other read-only buffers raise
+    TypeError, a variable-rate stream ValueError.  region: as for
+    decompress_region.  values: an ndarray of the region's shape and the
+    stream's dtype, any strides (no cast: another dtype raises TypeError,
+    another shape ValueError).  Only the blocks that intersect the region are
+    coded again; a block the region cuts through is decoded, overlaid and coded
+    again.  Every other byte of the stream stays.  Returns the number of blocks
+    rewritten.  1D to 3D arrays."""
+    if stream is None:
+        raise TypeError("stream cannot be None")
+    mv = memoryview(stream)
+    if mv.readonly:
+        raise TypeError("compress_region updates the stream in place: it needs a writable buffer "
+                        "(bytearray, writable memoryview or uint8 ndarray), not %s" % type(stream).__name__)
+    buf = np.frombuffer(mv, dtype=np.uint8)
+    if buf.size == 0 or buf.size % 8:
+        raise ValueError("stream of %d bytes is not a whole number of 64-bit words" % buf.size)
+    return _compress_region_at(buf.ctypes.data, buf.size, None, lambda shape: _region_box(region, shape), values,
+                               device)
+
+
+def _compress_region_bytes(data, coded_box, box, values, device):
+    """A new bytes object: the chunk stream `data` (bytes) with `box` rewritten
+    from `values`.  The copy is made and updated before the object is shared
+    (_bytes_target's rule), with the GIL released."""
+    n = len(data)
+    out, addr = _bytes_target(n)
+    ctypes.memmove(addr, _bytes_addr(data), n)
+    _compress_region_at(addr, n, coded_box, box, values, device)
+    return out
 
 
 def _decompress(compressed_data, ztype, shape, out=None, tolerance=-1, rate=-1, precision=-1, *, device=-1):
