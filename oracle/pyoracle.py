@@ -184,14 +184,20 @@ class Oracle:
         nwords = (end + 63) // 64
         return words[:nwords].copy(), int(end)
 
-    def decompress_words(self, words, shape, dtype, params, box=None, bit_offset=0, out=None):
+    def decompress_words(self, words, shape, dtype, params, box=None, bit_offset=0, out=None, strides=None,
+                         base=None):
+        """Decode into `out` (a fresh dense array when None).  `strides` (zfp
+        order, in elements; a zero entry means the dense default) and `base`
+        (the address of logical element 0) describe a strided destination, as
+        for compress_words; `out` then only keeps the memory alive."""
         ztype = TYPE_FLOAT if dtype == np.float32 else TYPE_DOUBLE
-        j = self.make_job(shape, ztype, params, None, box)
+        j = self.make_job(shape, ztype, params, strides, box)
         if out is None:
             out = np.zeros(shape, dtype=dtype)
         w = np.zeros(len(words) + 4, dtype=np.uint64)
         w[:len(words)] = words
-        end = self.lib.oz_decompress(ctypes.byref(j), out.ctypes.data, w.ctypes.data, bit_offset)
+        ptr = out.ctypes.data if base is None else base
+        end = self.lib.oz_decompress(ctypes.byref(j), ptr, w.ctypes.data, bit_offset)
         return out, int(end)
 
     def block_bits(self, arr, params):

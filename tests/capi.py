@@ -64,6 +64,8 @@ class ZfpCAPI:
         "zfp_field_4d": (vp, [vp, i32, sz, sz, sz, sz]),
         "zfp_field_free": (None, [vp]),
         "zfp_field_set_pointer": (None, [vp, vp]),
+        "zfp_field_set_stride_1d": (None, [vp, pd]),
+        "zfp_field_set_stride_2d": (None, [vp, pd, pd]),
         "zfp_field_set_stride_3d": (None, [vp, pd, pd, pd]),
         "zfp_field_set_stride_4d": (None, [vp, pd, pd, pd, pd]),
         "zfp_field_metadata": (u64, [vp]),
@@ -78,6 +80,8 @@ class ZfpCAPI:
         "zfp_read_header": (sz, [vp, vp, u32]),
         "zfp_chunk_alloc": (vp, []),
         "zfp_chunk_free": (None, [vp]),
+        "zfp_set_chunk_1d": (None, [vp, i32, i32]),
+        "zfp_set_chunk_2d": (None, [vp, i32, i32, i32, i32]),
         "zfp_set_chunk_3d": (None, [vp, i32, i32, i32, i32, i32, i32]),
         "zfp_set_chunk_4d": (None, [vp, i32, i32, i32, i32, i32, i32, i32, i32]),
         "zfp_optimal_parts_from_size": (vp, [i32, vp, ctypes.c_float, i32]),
@@ -141,7 +145,11 @@ class ZfpCAPI:
             f = self.lib.zfp_field_4d(ptr, t, *shp)
         if strided:
             st = [s // arr.itemsize for s in reversed(arr.strides)]
-            if arr.ndim == 3:
+            if arr.ndim == 1:
+                self.lib.zfp_field_set_stride_1d(f, *st)
+            elif arr.ndim == 2:
+                self.lib.zfp_field_set_stride_2d(f, *st)
+            elif arr.ndim == 3:
                 self.lib.zfp_field_set_stride_3d(f, *st)
             elif arr.ndim == 4:
                 self.lib.zfp_field_set_stride_4d(f, *st)
@@ -217,8 +225,10 @@ class ZfpCAPI:
         return bytes(buf[:n])
 
     def decompress(self, data, shape, dtype, mode, param=None, ztype=None, header=False, out=None,
-                   execution=None, index=None, strided=False):
-        """`strided`: the field takes `out`'s own strides (a transposed or sliced array)."""
+                   execution=None, index=None, strided=False, chunk=None, pad_bits=0):
+        """`strided`: the field takes `out`'s own strides (a transposed or sliced array).
+        `chunk`: decode that box with zfp_decompress_chunk.  `pad_bits`: the blocks
+        start after that many bits of `data` (skipped with stream_skip)."""
         dtype = np.dtype(dtype)
         if out is None:
             out = np.zeros(shape, dtype=dtype)
@@ -237,7 +247,14 @@ class ZfpCAPI:
             assert self.lib.zfp_read_header(zs, field, ZFP_HEADER_FULL)
         if index is not None:
             self.lib.zfp_stream_set_hip_index(zs, index)
-        n = self.lib.zfp_decompress(zs, field)
+        if pad_bits:
+            self.lib.stream_skip(bs, pad_bits)
+        if chunk is None:
+            n = self.lib.zfp_decompress(zs, field)
+        else:
+            ck = self.make_chunk(len(shape), chunk)
+            n = self.lib.zfp_decompress_chunk(zs, ck, field)
+            self.lib.zfp_chunk_free(ck)
         self.lib.stream_close(bs)
         self.lib.zfp_stream_close(zs)
         self.lib.zfp_field_free(field)
@@ -282,11 +299,15 @@ class ZfpCAPI:
     def make_chunk(self, ndim, box):
         """box: list of (f, e) per zfp axis (x first)."""
         ck = self.lib.zfp_chunk_alloc()
-        if ndim == 3:
+        if ndim == 1:
+            self.lib.zfp_set_chunk_1d(ck, box[0][0], box[0][1])
+        elif ndim == 2:
+            self.lib.zfp_set_chunk_2d(ck, box[0][0], box[1][0], box[0][1], box[1][1])
+        elif ndim == 3:
             self.lib.zfp_set_chunk_3d(ck, box[0][0], box[1][0], box[2][0], box[0][1], box[1][1], box[2][1])
         elif ndim == 4:
             self.lib.zfp_set_chunk_4d(ck, box[0][0], box[1][0], box[2][0], box[3][0],
                                       box[0][1], box[1][1], box[2][1], box[3][1])
         else:
-            raise ValueError("chunk helper covers 3D/4D")
+            raise ValueError("chunk helper covers 1D-4D")
         return ck

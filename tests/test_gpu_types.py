@@ -12,6 +12,10 @@ import zlib
 import numpy as np
 import pytest
 
+import layouts
+from pyoracle import params_accuracy, params_precision, params_rate, params_reversible
+from test_gpu_codec import MODES as CODEC_MODES
+
 pytestmark = pytest.mark.gpu
 
 TYPES = {np.dtype(np.int32): 1, np.dtype(np.int64): 2, np.dtype(np.float32): 3, np.dtype(np.float64): 4}
@@ -102,3 +106,142 @@ def test_threaded_chunks_sharing_pages(product, ref_capi, shape, dtype):
         zp._compress_data = [bytes(s) for s in streams]
         zp.decompress(nthreads=8)
         assert np.ascontiguousarray(zp.get_numpy_array()).tobytes() == want.tobytes()
+
+
+# ---------------------------------------------------------------------------
+# The generic per-lane codec on hard values: special floats in every mode and
+# at odd stream offsets, integers at the edge of their range.
+def _float_params(mode, param, ztype, dims):
+    if mode == "rate":
+        return params_rate(param, ztype, dims)
+    if mode == "precision":
+        return params_precision(param)
+    if mode == "accuracy":
+        return params_accuracy(param)
+    return param if mode == "expert" else params_reversible()
+
+
+# test_gpu_codec.MODES (its expert tuple pads short blocks to minbits) and an
+# expert tuple whose small maxbits truncates blocks
+HARD_MODES = CODEC_MODES + [("expert", (1, 40, 64, -1074))]
+_HARD = {}
+
+
+def _hard_field(dims, dtype):
+    """NaN, +-Inf, +-0, denormals, +-max, 1e-3..1e5 and whole blocks of denormal,
+    -0, 0 and NaN (layouts.special_field), one field per (dims, dtype)."""
+    key = (dims, np.dtype(dtype).name)
+    if key not in _HARD:
+        a = layouts.special_field(layouts.SHAPES[dims], np.dtype(dtype), np.random.default_rng(zlib.crc32(repr(key).encode())))
+        a.setflags(write=False)
+        _HARD[key] = a
+    return _HARD[key]
+
+
+@pytest.mark.parametrize("mode,param", HARD_MODES)
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("dims", [1, 2])
+def test_special_values_1d_2d_match_oracle(product, oracle, dims, dtype, mode, param):
+    a = _hard_field(dims, dtype)
+    ztype = TYPES[a.dtype]
+    params = _float_params(mode, param, ztype, dims)
+    words, end = oracle.compress_words(a, params)
+    want = words.view(np.uint8)[: (end + 63) // 64 * 8].tobytes()
+    ref_out, _ = oracle.decompress_words(words, a.shape, a.dtype, params)
+    product.last_index = None
+    got = product.compress(a, mode, param, ztype=ztype)
+    index = product.last_index
+    try:
+        assert got == want
+        for idx in ((index, None) if index else (None,)):  # the encoder's index, then the scan
+            out, n = product.decompress(want, a.shape, a.dtype, mode, param, ztype=ztype, index=idx)
+            assert n == len(want), (idx is None, product.lib.zfp_hip_last_error())
+            assert out.view(layouts.uint_of(a.dtype)).tobytes() == ref_out.view(layouts.uint_of(a.dtype)).tobytes(), \
+                (idx is None)
+    finally:
+        if index:
+            product.lib.zfp_hip_index_free(index)
+        product.last_index = None
+
+
+@pytest.mark.parametrize("mode,param", [("rate", 8), ("precision", 18)])
+@pytest.mark.parametrize("pad", [1, 63, 100])
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("dims", [1, 2])
+def test_special_values_1d_2d_at_bit_offsets(product, oracle, dims, dtype, pad, mode, param):
+    """Blocks that start at stream bit 1, 63 and 100 (stream_pad before the encode,
+    stream_skip before the decode) against the oracle at the same bit offset."""
+    a = _hard_field(dims, dtype)
+    ztype = TYPES[a.dtype]
+    params = _float_params(mode, param, ztype, dims)
+    words, end = oracle.compress_words(a, params, bit_offset=pad)
+    want = words.view(np.uint8)[: (end + 63) // 64 * 8].tobytes()
+    ref_out, _ = oracle.decompress_words(words, a.shape, a.dtype, params, bit_offset=pad)
+    product.last_index = None
+    got = product.compress(a, mode, param, ztype=ztype, pad_bits=pad)
+    index = product.last_index
+    try:
+        assert got == want
+        for idx in ((index, None) if index else (None,)):
+            out, n = product.decompress(want, a.shape, a.dtype, mode, param, ztype=ztype, index=idx, pad_bits=pad)
+            assert n == len(want), (idx is None, product.lib.zfp_hip_last_error())
+            assert out.view(layouts.uint_of(a.dtype)).tobytes() == ref_out.view(layouts.uint_of(a.dtype)).tobytes(), \
+                (idx is None)
+    finally:
+        if index:
+            product.lib.zfp_hip_index_free(index)
+        product.last_index = None
+
+
+@pytest.mark.parametrize("dtype", ["int32", "int64"])
+@pytest.mark.parametrize("dims", [1, 2, 3, 4])
+def test_full_range_integers_reversible(product, ref_capi, dims, dtype):
+    """Reversible mode on integers over the whole range of the type, with MIN,
+    MAX, -1 and 0: the round trip returns the input exactly (the truth is the
+    input; the transform's differences wrap) and the stream is the reference's
+    (which round-trips these fields too: checked on the CPU)."""
+    dtype = np.dtype(dtype)
+    a = layouts.edge_ints(layouts.SHAPES[dims], dtype, np.random.default_rng(dims), True)
+    info = np.iinfo(dtype)
+    assert {info.min, info.max, -1, 0} <= set(a.reshape(-1).tolist())
+    want = ref_capi.compress(a, "reversible", None)
+    product.last_index = None
+    got = product.compress(a, "reversible", None)
+    index = product.last_index
+    try:
+        for idx in (index, None):
+            out, n = product.decompress(got, a.shape, dtype, "reversible", None, index=idx)
+            assert n == len(got)
+            assert np.array_equal(out, a), (idx is None, "the round trip is not lossless")
+        assert got == want
+    finally:
+        if index:
+            product.lib.zfp_hip_index_free(index)
+        product.last_index = None
+
+
+@pytest.mark.parametrize("mode,param", [m for m in _modes(np.int32) if m[0] != "reversible"])
+@pytest.mark.parametrize("dtype", ["int32", "int64"])
+@pytest.mark.parametrize("dims", [1, 2, 3, 4])
+def test_wide_integers_lossy_match_reference(product, ref_capi, dims, dtype, mode, param):
+    """Rate and precision modes on integers spanning the documented lossy range,
+    |x| < 2^30 (int32) and < 2^62 (int64): the high bit planes are in use."""
+    dtype = np.dtype(dtype)
+    a = layouts.edge_ints(layouts.SHAPES[dims], dtype, np.random.default_rng(10 + dims), False)
+    lim = 1 << (np.iinfo(dtype).bits - 2)
+    assert np.abs(a).max() == lim - 1
+    want = ref_capi.compress(a, mode, param)
+    ref_out, _ = ref_capi.decompress(want, a.shape, dtype, mode, param)
+    product.last_index = None
+    got = product.compress(a, mode, param)
+    index = product.last_index
+    try:
+        assert got == want
+        for idx in ((index, None) if index else (None,)):
+            out, n = product.decompress(want, a.shape, dtype, mode, param, index=idx)
+            assert n == len(want)
+            assert out.tobytes() == ref_out.tobytes(), (idx is None)
+    finally:
+        if index:
+            product.lib.zfp_hip_index_free(index)
+        product.last_index = None

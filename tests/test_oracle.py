@@ -10,6 +10,7 @@
 import numpy as np
 import pytest
 
+import layouts
 from pyoracle import (TYPE_DOUBLE, TYPE_FLOAT, params_accuracy, params_precision, params_rate,
                       params_reversible)
 
@@ -108,6 +109,60 @@ def test_oracle_chunk_boxes_and_strides_match_reference(oracle, ref_capi, dtype)
     st = [s // t.itemsize for s in reversed(t.strides)] + [0]
     words, end = oracle.compress_words(t, params_precision(20), strides=st, base=t.ctypes.data)
     assert words.view(np.uint8)[: len(ref)].tobytes() == ref
+
+
+# ---------------- field layouts (tests/layouts.py) ----------------
+def _ref_or_none():
+    """The reference library where oracle/_ref is built, else None (no skip: the
+    oracle-only assertions of a layout test hold either way)."""
+    from pyoracle import REF_SO, have_ref
+    if not have_ref():
+        return None
+    from capi import ZfpCAPI
+    return ZfpCAPI(REF_SO)
+
+
+LAYOUT_CASES = [(d, l) for d in (1, 2, 3, 4) for l in layouts.layouts_for(d)]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("dims,layout", LAYOUT_CASES)
+def test_oracle_layout_strided_encode_and_decode(oracle, dims, layout, dtype):
+    """Strides, offsets and negative strides in the oracle itself, before the GPU
+    layout tests rely on it: a strided encode equals the encode of the same
+    values stored densely (and the reference library's encode of the strided
+    view), and a strided decode writes the dense decode's values through the
+    view and nothing outside it."""
+    shape = layouts.SHAPES[dims]
+    rng = np.random.default_rng(dims * 16 + layouts.LAYOUTS.index(layout))
+    a = _special_field(shape, dtype, rng)
+    ztype = TYPE_FLOAT if dtype == np.float32 else TYPE_DOUBLE
+    ref = _ref_or_none()
+    for mode, param in (("rate", layouts.FIXED_RATE[dims]), ("precision", 18), ("reversible", None)):
+        params = _params(mode, param, ztype, dims)
+        buf, view = layouts.make_view(a, layout)
+        assert layouts.bits(view).tobytes() == layouts.bits(a).tobytes()
+        st = layouts.zfp_strides(view)
+        dense_words, dense_end = oracle.compress_words(np.ascontiguousarray(view), params)
+        words, end = oracle.compress_words(view, params, strides=st, base=view.ctypes.data)
+        assert end == dense_end and words.tobytes() == dense_words.tobytes(), (mode, "encode")
+        assert layouts.guard_intact(buf, view)
+        if ref is not None:
+            got = ref.compress(view, mode, param, strided=True)
+            assert got == words.view(np.uint8)[: (end + 63) // 64 * 8].tobytes(), (mode, "reference encode")
+        want, want_end = oracle.decompress_words(words, shape, dtype, params)
+        dbuf, dview = layouts.make_view(a, layout, fill=False)
+        _, got_end = oracle.decompress_words(words, shape, dtype, params, out=dbuf, strides=st,
+                                             base=dview.ctypes.data)
+        assert got_end == want_end == end
+        assert layouts.bits(dview).tobytes() == layouts.bits(want).tobytes(), (mode, "decode")
+        assert layouts.guard_intact(dbuf, dview), (mode, "decode wrote outside the view")
+        if ref is not None:
+            rbuf, rview = layouts.make_view(a, layout, fill=False)
+            _, n = ref.decompress(got, shape, dtype, mode, param, out=rview, strided=True)
+            assert n == len(got)
+            assert layouts.bits(rview).tobytes() == layouts.bits(want).tobytes(), (mode, "reference decode")
+            assert layouts.guard_intact(rbuf, rview)
 
 
 # ---------------- integer golden tables ----------------

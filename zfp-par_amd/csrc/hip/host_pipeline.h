@@ -99,22 +99,30 @@ static int copy_box(Ctx* c, const Plan& p, void* h_base, void* d_base, size_t es
   if (to_host) {
     const size_t w0 = (size_t)(e[0] - g.f[0]) * es;
     const size_t nrows = p.dims >= 2 ? (size_t)(e[1] - g.f[1]) : 1;
-    const size_t pitch = nrows > 1 ? (size_t)g.s[1] * es : w0;
+    // a negative y stride (rows stored last to first): the 2D copy starts at
+    // the slice's last row, the lowest address, and the rows go back reversed
+    const int64_t sy = nrows > 1 ? g.s[1] : 0;
+    const bool flip = sy < 0;
+    const size_t pitch = nrows > 1 ? (size_t)(flip ? -sy : sy) * es : w0;
+    if (pitch < w0)
+      return fail("zfp_hip: host-resident decompression needs a y stride of at least the row length");
+    const int64_t low_row = flip ? (int64_t)(nrows - 1) * sy : 0;
     const uint64_t z0 = p.dims >= 3 ? g.f[2] : 0, z1 = p.dims >= 3 ? e[2] : 1;
     const uint64_t v0 = p.dims >= 4 ? g.f[3] : 0, v1 = p.dims >= 4 ? e[3] : 1;
     std::vector<char> tmp(w0 * nrows * (size_t)((z1 - z0) * (v1 - v0)));
     size_t k = 0;
     for (uint64_t w = v0; w < v1; w++)
       for (uint64_t z = z0; z < z1; z++, k++)
-        HIP_TRY(hipMemcpy2DAsync(tmp.data() + k * w0 * nrows, w0, (char*)d_base + slice_off(z, w) * (int64_t)es, pitch,
-                                 w0, nrows, hipMemcpyDeviceToHost, q));
+        HIP_TRY(hipMemcpy2DAsync(tmp.data() + k * w0 * nrows, w0,
+                                 (char*)d_base + (slice_off(z, w) + low_row) * (int64_t)es, pitch, w0, nrows,
+                                 hipMemcpyDeviceToHost, q));
     HIP_TRY(hipStreamSynchronize(q));
     k = 0;
     for (uint64_t w = v0; w < v1; w++)
       for (uint64_t z = z0; z < z1; z++, k++)
         for (size_t y = 0; y < nrows; y++)
           memcpy((char*)h_base + (slice_off(z, w) + (int64_t)y * (p.dims >= 2 ? g.s[1] : 0)) * (int64_t)es,
-                 tmp.data() + (k * nrows + y) * w0, w0);
+                 tmp.data() + (k * nrows + (flip ? nrows - 1 - y : y)) * w0, w0);
     return 1;
   }
   // row-wise 2D copies, one per (z, w) slice
