@@ -304,6 +304,14 @@ size_t zfp_decompress_chunk(zfp_stream* stream, const zfp_chunk* chunk, zfp_fiel
  * decoded; 1D to 3D fields.  zfp_true on success. */
 zfp_bool zfp_decompress_region(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
                                const zfp_chunk* region, zfp_field* out);
+/* MI355X addition: batched region decode.
+ * `nregions` regions of one stream in one GPU launch: every (regions[i], outs[i]) pair follows the contract of
+ * zfp_decompress_region (outs[i] has the region's type, dimensionality and extents, with its own pointer and
+ * strides; host or device memory, all of one kind).  Regions may overlap and repeat; the destinations must not
+ * overlap each other.  The stream is positioned at the first block and its position is left unchanged; its
+ * attached HIP index and device are used.  zfp_false, with nothing written, for a mismatch in any pair. */
+zfp_bool zfp_decompress_regions(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
+                                const zfp_chunk* regions, size_t nregions, zfp_field* const* outs);
 /* MI355X addition: region encode, the write twin of zfp_decompress_region.
  * Rewrite region [f,e) of `region` in the fixed-rate stream that codes `coded` (NULL: the whole field) of
  * `field` (type, extents; its data pointer is not used) from `in`, a field of the region's extents with its own

@@ -123,6 +123,46 @@ int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], cons
                               const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
                               int device, const zfp_hip_index* index, uint64_t* blocks_read);
 
+/* One region of a batch (zfp_hip_decompress_regions). */
+typedef struct zfp_hip_region {
+  uint64_t lo[4], hi[4];   /* as zfp_hip_decompress_region */
+  void* dst;               /* host or device memory */
+  int64_t dst_stride[4];   /* element strides */
+} zfp_hip_region;
+
+/*
+ * Batched region decode: `nregions` sub-boxes of the coded box of `job`, each
+ * into its own destination, in one kernel launch (the regions' blocks are
+ * dealt out to the launch's waves, whole waves per region).  Region i receives
+ * exactly what zfp_hip_decompress_region writes for (lo, hi, dst, dst_stride)
+ * of regions[i] -- bit for bit what a full decode holds there -- and nothing
+ * else is written.  Regions may overlap each other and may repeat (a block two
+ * regions touch is decoded twice); destinations that overlap each other are the
+ * caller's error and are not checked.  The destinations of one call are all
+ * host or all device memory: a mix returns 0 before any launch or copy.
+ * Checked before any GPU call, returning 0 with no destination written and
+ * *blocks_read untouched: a null `job`, `regions` or `words`, a null `dst` in
+ * any entry, any entry's region empty or outside the coded box (the message
+ * names the entry), a 4D job, more than 65,536 regions, and more than
+ * 2^32 - 1 lanes once every region is padded to whole waves of 64 blocks.  One
+ * bad entry fails the whole call.  nregions == 0 returns 1 with
+ * *blocks_read = 0 and makes no GPU call.
+ * Variable rate: `index` as for zfp_hip_decompress_region; a stale index
+ * repeats the whole batch with a scan (zfp_hip_last_stale_index).
+ * Host `words`: a fixed-rate call stages one span, from the first word of the
+ * lowest block any region needs to the last word of the highest plus one word
+ * of look-ahead -- for regions that lie far apart that is most of the stream;
+ * streams in device memory are the fast path.  A variable-rate host stream is
+ * staged whole.  Host destinations: the regions are decoded into dense device
+ * images and copied out one by one.
+ * *blocks_read (optional) receives the sum over the regions of
+ * zfp_hip_decompress_region's block count (padding lanes are not counted).
+ * zfp_hip_last_timing reports the one launch.
+ */
+int zfp_hip_decompress_regions(const zfp_hip_job* job, const zfp_hip_region* regions, uint64_t nregions,
+                               const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
+                               int device, const zfp_hip_index* index, uint64_t* blocks_read);
+
 /*
  * Region encode: rewrite the sub-box [lo, hi) (element granular, f <= lo < hi
  * <= e per axis) of the fixed-rate stream that codes the chunk box of `job`,

@@ -26,6 +26,7 @@ struct Ctx {
   Scratch scan_bm, scan_seg, scan_tiles, scan_pos;  // index scan of a stream without index
   zfp_hip_index scan_index;                         // index built by the scan
   Scratch chk;                                      // index verification word (DecodeArgs::idx_bad)
+  Scratch boxes;                                    // batched region decode: the records and wave_first
   uint32_t* idx_chk = nullptr;                      // set while a caller's index is being verified
   char* pin = nullptr;                              // pinned staging of small host copies (pin_take)
   size_t pin_used = 0;                              // bytes of it handed out in the current call
@@ -59,7 +60,7 @@ static void destroy_ctx(Ctx* c)
 {
   (void)hipSetDevice(c->device);
   for (Scratch* s : {&c->field, &c->words, &c->status, &c->partials, &c->misc, &c->ovf, &c->fpbuf, &c->scan_bm,
-                     &c->scan_seg, &c->scan_tiles, &c->scan_pos, &c->chk})
+                     &c->scan_seg, &c->scan_tiles, &c->scan_pos, &c->chk, &c->boxes})
     free_scratch(*s);
   index_release(&c->scan_index);
   if (c->pin)

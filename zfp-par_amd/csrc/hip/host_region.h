@@ -92,13 +92,18 @@ static int region_to_host(Ctx* c, const Plan& p, const RegionGeom& rg, const int
   return 1;
 }
 
-// One region decode with the given index (nullptr: the stream is scanned);
-// *stale and *scanned as decompress_once.
-static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const int64_t* dst_stride,
-                       const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
-                       const zfp_hip_index* index, bool plain_scan, bool* stale, bool* scanned)
+// The stream side of a region decode, shared by the single and the batched
+// call: the check word of a variable-rate index, ev[0], the stream on the
+// device and the kernel's RegionArgs.  [Blo, Bhi]: the lowest and highest
+// stream block needed.  A fixed-rate host stream is staged from Blo's first
+// word to Bhi's last plus the decoder's one look-ahead word, with bit0 rebased;
+// a variable-rate one whole, and its index is the caller's when it matches,
+// the scan's otherwise (*scanned), with its start table.  *lds: the dynamic
+// LDS of the launch.
+static int region_stream(Ctx* c, const Plan& p, uint64_t Blo, uint64_t Bhi, const uint64_t* words,
+                         uint64_t capacity_words, uint64_t bit_offset, const zfp_hip_index* index, bool plain_scan,
+                         bool* scanned, RegionArgs& a, size_t* lds)
 {
-  const bool dev_dst = is_device_ptr(dst);
   const bool dev_stream = is_device_ptr(words);
   const bool have_index = !p.fixed && index_matches(c, index, p, words, dev_stream, capacity_words, bit_offset);
   const bool scan = !p.fixed && !have_index;
@@ -111,7 +116,7 @@ static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const in
     c->idx_chk = (uint32_t*)c->chk.p;
   }
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  RegionArgs a{};
+  a = RegionArgs{};
   a.var = p.fixed ? 0 : 1;
   a.maxbits = p.cp.maxbits;
   a.idx_bad = c->idx_chk;
@@ -120,14 +125,6 @@ static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const in
     a.in_words = capacity_words;
     a.bit0 = bit_offset;
     if (!dev_stream) {
-      // the words from the first needed block's start to the last needed
-      // block's end, and the decoder's one look-ahead word
-      uint64_t Blo = 0, Bhi = 0, mul = 1;
-      for (int k = 0; k < 3; k++) {
-        Blo += mul * rg.rb0[k];
-        Bhi += mul * (rg.rb0[k] + rg.rnb[k] - 1);
-        mul *= p.g.nb[k];
-      }
       const uint64_t Wf = (bit_offset + Blo * (uint64_t)p.cp.maxbits) >> 6;
       const uint64_t We = std::min<uint64_t>(((bit_offset + (Bhi + 1) * (uint64_t)p.cp.maxbits + 63) >> 6) + 1,
                                              capacity_words);
@@ -168,42 +165,48 @@ static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const in
     a.idx_len = index->d_len;
     a.start = index->d_start;
   }
-  // destination: the caller's device array, or a dense image of the region
-  void* d_dst = dst;
-  if (!dev_dst) {
-    uint64_t count = 1;
-    for (int k = 0; k < p.dims; k++) {
-      rg.ds[k] = (int64_t)count;
-      count *= rg.hi[k] - rg.lo[k];
-    }
-    if (!ensure(c->field, count * p.es))
-      return 0;
-    d_dst = c->field.p;
-  }
-  rg.vec = region_vec_ok(rg, p.dims, d_dst) ? 1u : 0u;
   const uint32_t per_block = p.fixed ? p.cp.maxbits : p.max_len;
   a.W = (per_block + 63) / 64 + 1;  // peek64 at the budget end reads one word past it
   a.swp = a.W | 1;
   a.wmagic = (uint32_t)((0x100000000ull + a.W - 1) / a.W);
-  const size_t lds = (size_t)kWavesPerGroup * 64 * a.swp * 8;
-  if (lds + kLutBytes + kWavesPerGroup * 64 * 8 > 160 * 1024)
+  *lds = (size_t)kWavesPerGroup * 64 * a.swp * 8;
+  if (*lds + kLutBytes + kWavesPerGroup * 64 * 8 > 160 * 1024)
     return fail("zfp_hip: block size too large for LDS staging (%u bits)", per_block);
-  const dim3 grid((unsigned)((rg.nrblocks + 64 * kWavesPerGroup - 1) / (64 * kWavesPerGroup)));
-  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-  launch_decode_region(p.type, p.dims, p.cp.minexp < kMinExp, hi_planes<double>(p) && p.type == 4, c->stream, grid,
-                       lds, d_dst, p.g, p.cp, rg, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-  const uint32_t* pchk = nullptr;  // the check word, fetched with the call's last synchronize
+  return 1;
+}
+
+// First and last block of the region in the stream (raster order of the coded box)
+static void region_block_span(const Plan& p, const RegionGeom& rg, uint64_t* Blo, uint64_t* Bhi)
+{
+  uint64_t mul = 1;
+  *Blo = *Bhi = 0;
+  for (int k = 0; k < 3; k++) {
+    *Blo += mul * rg.rb0[k];
+    *Bhi += mul * (rg.rb0[k] + rg.rnb[k] - 1);
+    mul *= p.g.nb[k];
+  }
+}
+
+// After the launch (ev[2] recorded): the check word's copy is queued, to be
+// fetched with the call's last synchronize (*pchk; nullptr: region_finish
+// fetches it with a copy of its own).
+static int region_queue_check(Ctx* c, const uint32_t** pchk)
+{
+  *pchk = nullptr;
   if (c->idx_chk) {
     uint32_t* q = (uint32_t*)pin_take(c, 4);
     if (q) {
       HIP_TRY(hipMemcpyAsync(q, c->chk.p, 4, hipMemcpyDeviceToHost, c->stream));
-      pchk = q;
+      *pchk = q;
     }
   }
-  if (!dev_dst && !region_to_host(c, p, rg, dst_stride, dst, d_dst))
-    return 0;
+  return 1;
+}
+
+// The end of a region decode: ev[3], the synchronize, the timing and the
+// verdict of the check word (*stale).
+static int region_finish(Ctx* c, const uint32_t* pchk, bool* stale)
+{
   HIP_TRY(hipEventRecord(c->ev[3], c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   record_timing(c);
@@ -220,4 +223,44 @@ static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const in
       *stale = true;
   }
   return 1;
+}
+
+// One region decode with the given index (nullptr: the stream is scanned);
+// *stale and *scanned as decompress_once.
+static int region_once(Ctx* c, const Plan& p, RegionGeom rg, void* dst, const int64_t* dst_stride,
+                       const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
+                       const zfp_hip_index* index, bool plain_scan, bool* stale, bool* scanned)
+{
+  const bool dev_dst = is_device_ptr(dst);
+  uint64_t Blo, Bhi;
+  region_block_span(p, rg, &Blo, &Bhi);
+  RegionArgs a;
+  size_t lds;
+  if (!region_stream(c, p, Blo, Bhi, words, capacity_words, bit_offset, index, plain_scan, scanned, a, &lds))
+    return 0;
+  // destination: the caller's device array, or a dense image of the region
+  void* d_dst = dst;
+  if (!dev_dst) {
+    uint64_t count = 1;
+    for (int k = 0; k < p.dims; k++) {
+      rg.ds[k] = (int64_t)count;
+      count *= rg.hi[k] - rg.lo[k];
+    }
+    if (!ensure(c->field, count * p.es))
+      return 0;
+    d_dst = c->field.p;
+  }
+  rg.vec = region_vec_ok(rg, p.dims, d_dst) ? 1u : 0u;
+  const dim3 grid((unsigned)((rg.nrblocks + 64 * kWavesPerGroup - 1) / (64 * kWavesPerGroup)));
+  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+  launch_decode_region(p.type, p.dims, p.cp.minexp < kMinExp, hi_planes<double>(p) && p.type == 4, c->stream, grid,
+                       lds, d_dst, p.g, p.cp, rg, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+  const uint32_t* pchk;
+  if (!region_queue_check(c, &pchk))
+    return 0;
+  if (!dev_dst && !region_to_host(c, p, rg, dst_stride, dst, d_dst))
+    return 0;
+  return region_finish(c, pchk, stale);
 }

@@ -6,18 +6,6 @@
 #include "host_region.h"
 #include "kernels_region_enc.h"
 
-// First and last block of the region in the stream (raster order of the coded box)
-static void region_block_span(const Plan& p, const RegionGeom& rg, uint64_t* Blo, uint64_t* Bhi)
-{
-  uint64_t mul = 1;
-  *Blo = *Bhi = 0;
-  for (int k = 0; k < 3; k++) {
-    *Blo += mul * rg.rb0[k];
-    *Bhi += mul * (rg.rb0[k] + rg.rnb[k] - 1);
-    mul *= p.g.nb[k];
-  }
-}
-
 // Everything that is checked before any GPU call: plan_region's checks, fixed
 // rate, and that the stream holds the last needed block's last bit.
 static int plan_region_enc(const zfp_hip_job* job, const uint64_t* lo, const uint64_t* hi, const void* src,

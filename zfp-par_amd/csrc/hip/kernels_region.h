@@ -9,6 +9,8 @@
 //                     stages its blocks into LDS slots cooperatively, each
 //                     lane decodes with decode_block3 / decode_block_n and
 //                     stores the part of its block that lies in the region.
+//                     The body is region_wave, which decode3_boxes
+//                     (kernels_boxes.h) runs per region of a batch.
 //  build_start_table  the start bit of every block from the block index's
 //                     per-block lengths and per-wave bases.
 //
@@ -217,29 +219,23 @@ struct RegionArgs {
   uint32_t* idx_bad;        // as DecodeArgs::idx_bad
 };
 
+// One wave's share of a region: its 64 region blocks from `first` on (`live`:
+// first < rg.nrblocks, wave-uniform), as lane `lane` of wave `wv` of the
+// workgroup.  `sq` is the workgroup's squeeze table,
+// `spos` its kWavesPerGroup * 64 positions, `lds` the staging slots.
+//
 // The staging is decode3's: thread t copies word j of block l for t = l W + j,
 // funnel-shifted so the block starts at bit 0 of its slot.  A block's first
 // word and shift come from the lane's own 64-bit position, kept in LDS: the
 // blocks of a wave are x-runs of the region's rows, not one stream segment.
-template <typename S, bool REV, bool HI = false, int D = 3>
-__global__ __launch_bounds__(256, 1) void decode3_region(S* __restrict__ dst, Geometry g, CodecParams cp,
-                                                        RegionGeom rg, RegionArgs a)
+template <typename S, bool REV, bool HI, int D>
+__device__ __forceinline__ void region_wave(S* __restrict__ dst, const Geometry& g, const CodecParams& cp,
+                                            const RegionGeom& rg, const RegionArgs& a, uint64_t first, bool live,
+                                            int lane, int wv, const uint32_t* sq, uint64_t* spos, uint64_t* lds)
 {
-  __shared__ uint32_t sq[256];
-  __shared__ uint64_t spos[kWavesPerGroup * 64];
-  extern __shared__ uint64_t lds[];
-  const int lane = threadIdx.x & 63;
-  // every wave writes the whole (identical) table: no workgroup barrier below
-#pragma unroll
-  for (int k = 0; k < 4; k++)
-    sq[lane + 64 * k] = squeeze_entry(lane + 64 * k);
-  const int wv = threadIdx.x >> 6;
   uint64_t* wslot = lds + (size_t)wv * 64 * a.swp;
-  const uint64_t first = ((uint64_t)blockIdx.x * kWavesPerGroup + wv) * 64;
-  const bool live = first < rg.nrblocks;
   const uint64_t q = first + lane;
   const bool act = q < rg.nrblocks;
-
   uint64_t pos = 0;
   uint32_t len = 0;
   if (act) {
@@ -304,6 +300,23 @@ __global__ __launch_bounds__(256, 1) void decode3_region(S* __restrict__ dst, Ge
   region_scatter<S, D>(v, dst, rg, region_pos<D>(g, rg, (uint32_t)q));
   if (a.idx_bad && used != len)
     atomicOr(a.idx_bad, 1u);
+}
+
+template <typename S, bool REV, bool HI = false, int D = 3>
+__global__ __launch_bounds__(256, 1) void decode3_region(S* __restrict__ dst, Geometry g, CodecParams cp,
+                                                        RegionGeom rg, RegionArgs a)
+{
+  __shared__ uint32_t sq[256];
+  __shared__ uint64_t spos[kWavesPerGroup * 64];
+  extern __shared__ uint64_t lds[];
+  const int lane = threadIdx.x & 63;
+  // every wave writes the whole (identical) table: no workgroup barrier below
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    sq[lane + 64 * k] = squeeze_entry(lane + 64 * k);
+  const int wv = threadIdx.x >> 6;
+  const uint64_t first = ((uint64_t)blockIdx.x * kWavesPerGroup + wv) * 64;
+  region_wave<S, REV, HI, D>(dst, g, cp, rg, a, first, first < rg.nrblocks, lane, wv, sq, spos, lds);
 }
 
 // Launchers (zfp_region.hip holds every instantiation).  type: zfp_type (1

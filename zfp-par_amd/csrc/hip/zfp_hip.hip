@@ -27,6 +27,7 @@
 #include "host_pipeline.h"     // host <-> device box copies, the slab pipeline
 #include "host_region.h"       // region decode: validation, start table, launch, copy-out
 #include "host_region_enc.h"   // region encode: validation, source image, launch, copy-back
+#include "host_boxes.h"        // batched region decode: validation, the region table, launch, copy-out
 
 // ---------------------------------------------------------------------------
 // How every entry point that uses the device begins: the job's plan, the
@@ -359,6 +360,50 @@ int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], cons
   return lease.done(ok);
 }
 
+int zfp_hip_decompress_regions(const zfp_hip_job* job, const zfp_hip_region* regions, uint64_t nregions,
+                               const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset, int device,
+                               const zfp_hip_index* index, uint64_t* blocks_read)
+{
+  // (as zfp_hip_decompress_region: everything is validated before the first GPU call)
+  Plan p;
+  BoxesPlan bp;
+  std::vector<BoxRecord> rec;  // (outlives the lease: it may have to wait for the table's copy)
+  if (!plan_regions(job, regions, nregions, words, p, bp))
+    return 0;
+  if (nregions == 0) {
+    if (blocks_read)
+      *blocks_read = 0;
+    return 1;
+  }
+  if (zfp_hip_device_count() <= 0)
+    return fail("zfp_hip_decompress_regions: no HIP device available");
+  CtxLease lease;
+  lease.c = acquire_ctx(device);
+  if (!lease.c)
+    return 0;
+  Ctx* c = lease.c;
+  t_timing = Timing{};
+  bool stale = false, scanned = false;
+  auto once = [&](const zfp_hip_index* x, bool plain) {
+    stale = false;
+    return regions_once(c, p, bp, rec, regions, words, capacity_words, bit_offset, x, plain, &stale, &scanned);
+  };
+  int ok = once(index, false);
+  if (ok && stale) {  // as zfp_hip_decompress: the whole batch again with the scan, then a scan of plain passes
+    const bool plain = scanned;
+    ok = once(nullptr, plain);
+    if (ok && stale && !plain)
+      ok = once(nullptr, true);
+    t_timing.stale_index = true;
+    if (ok && stale)
+      return fail("zfp_hip_decompress_regions: decoded block lengths disagree with the stream's plain scan "
+                  "(corrupt stream)");
+  }
+  if (ok && blocks_read)
+    *blocks_read = bp.blocks;
+  return lease.done(ok);
+}
+
 int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4], const void* src,
                             const int64_t src_stride[4], uint64_t* words, uint64_t capacity_words,
                             uint64_t bit_offset, int device, uint64_t* blocks_written)
@@ -580,7 +625,7 @@ size_t zfp_hip_scratch_bytes(void)
   size_t b = 0;
   for (Ctx* c : g_idle) {
     for (const Scratch* s : {&c->field, &c->words, &c->status, &c->partials, &c->misc, &c->ovf, &c->scan_bm, &c->scan_seg,
-                             &c->scan_tiles, &c->scan_pos})
+                             &c->scan_tiles, &c->scan_pos, &c->boxes})
       b += s->bytes;
     b += c->scan_index.cap_blocks * 2 + c->scan_index.cap_waves * 8;
   }

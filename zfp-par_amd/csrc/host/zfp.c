@@ -1163,34 +1163,15 @@ static size_t decompress_exec(zfp_stream* zfp, const zfp_chunk* chunk, zfp_field
   return stream_size(s);
 }
 
-/* Region decode (no reference equivalent): the blocks of `coded` that intersect
- * `region`, written into `out` -- zfp_hip_decompress_region with the stream's
- * attached index, its device and its bit position, which stays where it is. */
-zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
-                               const zfp_chunk* region, zfp_field* out)
+/* A (region, out) pair of region decode: `out` has the field's type and
+ * dimensionality `d` and the region's extents.  Fills the region's corners and
+ * the destination's element strides. */
+static zfp_bool region_pair(const zfp_field* field, uint d, const zfp_chunk* region, const zfp_field* out, uint64* lo,
+                            uint64* hi, int64_t* ds)
 {
-  bitstream* s;
-  zfp_hip_job job;
-  zfp_chunk whole;
-  zfp_hip_index* index = NULL;
   ptrdiff_t st[4];
-  uint64 lo[4], hi[4];
-  int64_t ds[4];
-  uint d;
-  if (!zfp || !zfp->stream || !field || !region || !out || !out->data)
+  if (!region || !out || !out->data || field->type != out->type || zfp_field_dimensionality(out) != d)
     return zfp_false;
-  s = zfp->stream;
-  d = zfp_field_dimensionality(field);
-  if (field->type != out->type || zfp_field_dimensionality(out) != d)
-    return zfp_false;
-  if (!coded) {
-    whole.fx = whole.fy = whole.fz = whole.fw = 0;
-    whole.ex = field->nx;
-    whole.ey = field->ny;
-    whole.ez = field->nz;
-    whole.ew = field->nw;
-    coded = &whole;
-  }
   {
     const size_t f[4] = {region->fx, region->fy, region->fz, region->fw};
     const size_t e[4] = {region->ex, region->ey, region->ez, region->ew};
@@ -1204,6 +1185,39 @@ zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zf
         return zfp_false;
     }
   }
+  return zfp_true;
+}
+
+static void whole_chunk(zfp_chunk* whole, const zfp_field* field)
+{
+  whole->fx = whole->fy = whole->fz = whole->fw = 0;
+  whole->ex = field->nx;
+  whole->ey = field->ny;
+  whole->ez = field->nz;
+  whole->ew = field->nw;
+}
+
+/* Region decode (no reference equivalent): the blocks of `coded` that intersect
+ * `region`, written into `out` -- zfp_hip_decompress_region with the stream's
+ * attached index, its device and its bit position, which stays where it is. */
+zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
+                               const zfp_chunk* region, zfp_field* out)
+{
+  bitstream* s;
+  zfp_hip_job job;
+  zfp_chunk whole;
+  zfp_hip_index* index = NULL;
+  uint64 lo[4], hi[4];
+  int64_t ds[4];
+  if (!zfp || !zfp->stream || !field)
+    return zfp_false;
+  s = zfp->stream;
+  if (!region_pair(field, zfp_field_dimensionality(field), region, out, lo, hi, ds))
+    return zfp_false;
+  if (!coded) {
+    whole_chunk(&whole, field);
+    coded = &whole;
+  }
   job_from(&job, zfp, coded, field);
   if (variable_rate(zfp, field)) {
     ext_entry* x = ext_find(zfp, 0);
@@ -1215,6 +1229,51 @@ zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zf
     return zfp_false;
   }
   return zfp_true;
+}
+
+/* Batched region decode: every (regions[i], outs[i]) pair as
+ * zfp_decompress_region, in one zfp_hip_decompress_regions call.  A mismatch
+ * in any pair fails the call before anything is written. */
+zfp_bool zfp_decompress_regions(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
+                                const zfp_chunk* regions, size_t nregions, zfp_field* const* outs)
+{
+  bitstream* s;
+  zfp_hip_job job;
+  zfp_chunk whole;
+  zfp_hip_index* index = NULL;
+  zfp_hip_region* r;
+  zfp_bool ok = zfp_true;
+  uint d;
+  if (!zfp || !zfp->stream || !field || (nregions && (!regions || !outs)))
+    return zfp_false;
+  s = zfp->stream;
+  d = zfp_field_dimensionality(field);
+  r = (zfp_hip_region*)malloc((nregions ? nregions : 1) * sizeof(*r));
+  if (!r)
+    return zfp_false;
+  for (size_t i = 0; ok && i < nregions; i++) {
+    ok = outs[i] && region_pair(field, d, &regions[i], outs[i], r[i].lo, r[i].hi, r[i].dst_stride);
+    if (ok)
+      r[i].dst = outs[i]->data;
+  }
+  if (ok) {
+    if (!coded) {
+      whole_chunk(&whole, field);
+      coded = &whole;
+    }
+    job_from(&job, zfp, coded, field);
+    if (variable_rate(zfp, field)) {
+      ext_entry* x = ext_find(zfp, 0);
+      index = x ? x->index : NULL;
+    }
+    if (!zfp_hip_decompress_regions(&job, r, nregions, s->begin, (uint64)(s->end - s->begin), stream_rtell(s),
+                                    stream_device(zfp), index, NULL)) {
+      report("zfp_decompress_regions");
+      ok = zfp_false;
+    }
+  }
+  free(r);
+  return ok;
 }
 
 /* Region encode (no reference equivalent): the blocks of `coded` that intersect

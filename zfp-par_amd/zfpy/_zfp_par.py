@@ -22,7 +22,7 @@ from multiprocessing.sharedctypes import RawArray
 import numpy as np
 
 from .zfpy_c import (_compress_portion, _compress_region_bytes, _decompress_portion, _decompress_region_stream,
-                     _fixed_rate, _region_box, device_count, zfp_chunkit)
+                     _decompress_regions_stream, _fixed_rate, _region_box, device_count, zfp_chunkit)
 
 _TYPECODE = {"float32": "f", "float64": "d", "int32": "i", "int64": "q"}
 _ITEMSIZE = {"float32": 4, "float64": 8, "int32": 4, "int64": 8}
@@ -153,6 +153,42 @@ class zfp_p:
         with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
             pool.starmap(one, tasks)
         return out
+
+    def decompress_regions(self, regions, nthreads=-1):
+        """Many regions of the compressed array (each as for decompress_region) as a list of new
+        ndarrays; the shared array is not touched.  Every chunk that any region touches makes one
+        batched call on the thread pool for its parts of all the regions, each part written into its
+        place in its region's array, with the chunk's kept block index."""
+        if nthreads == -1:
+            nthreads = cpu_count()
+        data = self._compress_data
+        ck = self._chunkit
+        if len(data) != ck.get_nchunks():
+            raise RuntimeError("no compressed data for this partition (call compress first)")
+        nd = ck.ndim
+        boxes = [_region_box(region, tuple(ck.ns_python)) for region in regions]
+        outs = [np.empty(tuple(e - f for f, e in box), dtype=ck.dtype) for box in boxes]
+        tasks = []
+        for i in range(len(data)):
+            coded = list(reversed(ck.boxes[i][:nd]))  # numpy axis order
+            parts, views = [], []
+            for box, out in zip(boxes, outs):
+                part = [(max(f, cf), min(e, ce)) for (f, e), (cf, ce) in zip(box, coded)]
+                if all(f < e for f, e in part):
+                    parts.append(part)
+                    views.append(out[tuple(slice(f - f0, e - f0) for (f, e), (f0, _) in zip(part, box))])
+            if parts:
+                tasks.append((i, coded, parts, views))
+
+        def one(i, coded, parts, views):
+            blob = getattr(data[i], "block_index", None)
+            if blob is None and i < len(self._index_of) and self._index_of[i][0] is data[i]:
+                blob = self._index_of[i][1]
+            _decompress_regions_stream(data[i], coded, parts, views, self._device_of(i), blob)
+
+        with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
+            pool.starmap(one, tasks)
+        return outs
 
     def compress_region(self, region, values=None, nthreads=-1):
         """Code the elements `region` again, from `values` (an ndarray of the region's shape and the

@@ -61,6 +61,7 @@ for _name, _res, _args in [
     ("zfp_compress", _sz, [_vp, _vp]), ("zfp_decompress", _sz, [_vp, _vp]),
     ("zfp_compress_chunk", _sz, [_vp, _vp, _vp]), ("zfp_decompress_chunk", _sz, [_vp, _vp, _vp]),
     ("zfp_decompress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
+    ("zfp_decompress_regions", _i32, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zfp_compress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
     ("stream_rtell", _u64, [_vp]), ("stream_wseek", None, [_vp, _u64]),
     ("zfp_write_header", _sz, [_vp, _vp, _u32]), ("zfp_read_header", _sz, [_vp, _vp, _u32]),
@@ -555,6 +556,95 @@ def decompress_region(compressed_data, region, *, device=-1):
     whole axis.  1D to 3D arrays."""
     return _decompress_region_stream(compressed_data, None, lambda shape: _region_box(region, shape), None, device,
                                      getattr(compressed_data, "block_index", None))
+
+
+def _decompress_regions_into(stream, field, coded, boxes, outs, blob):
+    """One zfp_decompress_regions call: box i of `boxes` ([(first, end)] per
+    numpy axis) into the ndarray outs[i] of the box's shape, from a stream
+    positioned after its header.  coded: as _decompress_region_into."""
+    n = len(boxes)
+    cks = (_Chunk * max(n, 1))()
+    ofields = (_vp * max(n, 1))()
+    idx = None
+    try:
+        for i, (box, out) in enumerate(zip(boxes, outs)):
+            for (f, e), ax in zip(reversed(box), "xyzw"):
+                setattr(cks[i], "f" + ax, f)
+                setattr(cks[i], "e" + ax, e)
+            ofields[i] = _make_field(out.ctypes.data, dtype_to_ztype(out.dtype), list(reversed(out.shape)),
+                                     [s // out.itemsize for s in reversed(out.strides)])
+        idx = _attach_index(stream, blob)
+        ret = _lib.zfp_decompress_regions(stream, field, ctypes.byref(coded) if coded is not None else None,
+                                          cks, n, ofields)
+    finally:
+        if idx:
+            _lib.zfp_stream_set_hip_index(stream, None)
+            _lib.zfp_hip_index_free(idx)
+        for f in ofields:
+            if f:
+                _lib.zfp_field_free(f)
+    if not ret:
+        raise RuntimeError("error during zfp batched region decompression")
+    return outs
+
+
+def _decompress_regions_stream(compressed_data, coded_box, boxes, outs, device, blob):
+    """The regions `boxes` of a stream with a full header that codes
+    `coded_box` (numpy axis order; None: the whole field) into `outs` (None:
+    new C-contiguous arrays), with one native call; the list of arrays.
+    boxes: a list of [(first, end)] per numpy axis, or a function of the
+    array's shape that returns it."""
+    if compressed_data is None:
+        raise TypeError("compressed_data cannot be None")
+    ibuf, buf = _in_buffer(compressed_data)
+    field = _lib.zfp_field_alloc()
+    bstream = _lib.stream_open(buf, ibuf.size)
+    stream = _lib.zfp_stream_open(bstream)
+    try:
+        if device >= 0:
+            _lib.zfp_stream_set_hip_device(stream, device)
+        if _lib.zfp_read_header(stream, field, HEADER_FULL) == 0:
+            raise ValueError("Failed to read required zfp header")
+        fld = ctypes.cast(field, ctypes.POINTER(_Field)).contents
+        shape = tuple(n for n in (fld.nw, fld.nz, fld.ny, fld.nx) if n > 0)
+        dtype = ztype_to_dtype(fld.type)
+        if callable(boxes):
+            boxes = boxes(shape)
+        shapes = [tuple(e - f for f, e in box) for box in boxes]
+        if outs is None:
+            outs = [np.empty(sh, dtype=dtype) for sh in shapes]
+        else:
+            outs = list(outs)
+            if len(outs) != len(boxes):
+                raise ValueError("%d output arrays for %d regions" % (len(outs), len(boxes)))
+            for i, (o, sh) in enumerate(zip(outs, shapes)):
+                if not isinstance(o, np.ndarray):
+                    raise TypeError("out[%d] is not an ndarray" % i)
+                if o.dtype != dtype:
+                    raise TypeError("out[%d] has dtype %s, the stream codes %s" % (i, o.dtype, np.dtype(dtype)))
+                if o.shape != sh:
+                    raise ValueError("out[%d] has shape %s, its region has shape %s" % (i, o.shape, sh))
+        coded = _chunk_of(list(reversed(coded_box))) if coded_box is not None else None
+        return _decompress_regions_into(stream, field, coded, boxes, outs, blob)
+    finally:
+        _lib.zfp_field_free(field)
+        _lib.zfp_stream_close(stream)
+        _lib.stream_close(bstream)
+
+
+def decompress_regions(compressed_data, regions, *, out=None, device=-1):
+    """Many regions of the array a stream with a full header codes, decoded
+    with one native call and one GPU launch: a list with, for every entry of
+    `regions` (each what decompress_region accepts), what
+    decompress_numpy(compressed_data)[region] holds, as new C-contiguous
+    arrays.  With `out` -- a sequence of ndarrays of the regions' shapes and the
+    stream's dtype, with any strides; list(batch) for the crops of a
+    (N, d, h, w) array -- those arrays are filled and returned.  Regions may
+    overlap and repeat.  1D to 3D arrays."""
+    regions = list(regions)
+    return _decompress_regions_stream(compressed_data, None,
+                                      lambda shape: [_region_box(r, shape) for r in regions], out, device,
+                                      getattr(compressed_data, "block_index", None))
 
 
 _ZFP_MIN_EXP = -1074
