@@ -628,6 +628,10 @@ __device__ __forceinline__ void coeffs_from_planes_hi(int64_t (&q)[64], const ui
   }
 }
 
+// The largest maxprec at which a double block codes planes 32..63 only (HI
+// below): the launchers' choice of the HI kernels (host_launch.h hi_planes).
+constexpr uint32_t kHiPlanesMaxPrec = 32;
+
 __device__ __forceinline__ uint32_t precision3(int emax, const CodecParams& cp)
 {
   int p = emax - cp.minexp + 2 * 3 + 2;
@@ -771,6 +775,17 @@ __device__ __forceinline__ int lossy_emax_cast(int64_t (&q)[64], double (&v)[64]
 #define ZFP_PHASE_BARRIER() ((void)0)
 #endif
 
+// Where the fixed-rate coder applies (the launchers' rule for the aligned
+// kernels, host_launch.h aligned_encode): it codes every plane until the budget
+// is spent, so no block may have a precision limit below the integer width --
+// neither from maxprec nor from minexp (emax - minexp + 8 planes: with an
+// accuracy floor above ZFP_MIN_EXP small blocks stop early and are padded).
+template <typename S>
+__host__ __device__ constexpr bool fixed_rate_coder_applies(const CodecParams& cp)
+{
+  return cp.minbits == cp.maxbits && cp.maxprec >= (uint32_t)Traits<S>::kIntPrec && cp.minexp == kMinExp;
+}
+
 // Fixed-rate block (maxprec >= intprec, minbits == maxbits): encodef.c:63-90 +
 // encode.c:260-280 with every lane on one control path.  An all-zero block
 // (e == 0: the single bit "0", then padding) runs the transform and the coder
@@ -869,8 +884,9 @@ __device__ __forceinline__ uint32_t encode_block3(OrSlot& w, const uint32_t* lut
     if (same) {
       uint32_t e = (uint32_t)(emax + T::kEbias);
       if (!e) {
-        // a single 0 bit (already zero in the slot)
-        return 1u < cp.minbits ? cp.minbits : 1u;
+        // a single 0 bit (already zero in the slot), not padded to minbits:
+        // revencodef.c writes the bit and returns, though revdecodef.c skips minbits there
+        return 1u;
       }
       w.head(1u | (e << 2));
       bits = 2 + kE;

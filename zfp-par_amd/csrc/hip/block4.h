@@ -651,7 +651,7 @@ __device__ __forceinline__ uint32_t encode_block4(Place&& place, const uint32_t*
     OrSlot os{reinterpret_cast<uint64_t*>(d), jmax};
     const uint32_t e = (uint32_t)(emax + T::kEbias);
     if (same && !e)
-      return 1u < cp.minbits ? cp.minbits : 1u;  // a single 0 bit
+      return 1u;  // a single 0 bit, not padded to minbits (revencodef.c, see block3.h)
     uint32_t bits;
     if (same) {
       if (r == 0u) os.head(1u | (e << 2));

@@ -269,7 +269,7 @@ __device__ __forceinline__ uint32_t encode_block_n(OrSlot& w, const uint32_t* lu
     if (same) {
       const uint32_t e = (uint32_t)(emax + T::kEbias);
       if (!e)
-        return 1u < cp.minbits ? cp.minbits : 1u;  // a single 0 bit
+        return 1u;  // a single 0 bit, not padded to minbits (revencodef.c, see block3.h)
       w.head(1u | (e << 2));
       bits = 2 + kE;
     } else {

@@ -36,7 +36,7 @@ static uint64_t head_keep_mask(const Head& h, uint32_t g0) { return h.keep && g0
 template <typename S>
 static bool hi_planes(const Plan& p)
 {
-  return std::is_same<S, double>::value && p.dims == 3 && p.cp.maxprec <= 32;
+  return std::is_same<S, double>::value && p.dims == 3 && p.cp.maxprec <= kHiPlanesMaxPrec;
 }
 
 // 1D/2D blocks and integer fields: the generic per-lane codec (blockn.h),
@@ -327,11 +327,19 @@ static int run_encode4(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_out,
   return fail("zfp_hip: overflow pool exhausted with full-size slots");
 }
 
+// LDS slots of the aligned kernels: one of sdw dwords per lane (dwords from 2 sw on are spare)
+static uint32_t aligned_slot_dwords(const Plan& p) { return slot_dwords_for(p.cp.maxbits) | 1u; }
+static size_t aligned_lds_bytes(const Plan& p) { return (size_t)kWavesPerGroup * 64 * aligned_slot_dwords(p) * 4; }
+
 // launch_encode queues one kernel between ev[1] and ev[2] and nothing else:
-// the aligned fixed-rate path (the condition below) at a word-aligned start
+// the aligned fixed-rate path (the condition below) at a word-aligned start.
+// A block too long for the aligned slots (above 77 words: float rate 80) takes the
+// general path, whose slots are sized by what a block can code, not by its padding.
 static bool aligned_encode(const Plan& p)
 {
-  return p.type >= 3 && p.fixed && (p.cp.maxbits % 64) == 0 && p.cp.maxprec >= (p.dbl ? 64u : 32u) && p.dims == 3;
+  return p.type >= 3 && p.fixed && (p.cp.maxbits % 64) == 0 && p.dims == 3 &&
+         (p.dbl ? fixed_rate_coder_applies<double>(p.cp) : fixed_rate_coder_applies<float>(p.cp)) &&
+         aligned_lds_bytes(p) + sizeof(CoderTables) <= 160 * 1024;  // the kernels' static LDS: the coder tables
 }
 
 static bool one_kernel_encode(const Plan& p, uint32_t g0) { return g0 == 0 && aligned_encode(p); }
@@ -352,12 +360,10 @@ static int launch_encode(Ctx* c, const Plan& p, const S* d_field, uint64_t* d_ou
   if constexpr (!kIntField<S>)
   if (aligned_encode(p)) {
     const uint32_t sw = p.cp.maxbits / 64;
-    const uint32_t sdw = slot_dwords_for(p.cp.maxbits) | 1u;  // dwords from 2 sw on are spare
+    const uint32_t sdw = aligned_slot_dwords(p);
     auto magic_of = [](uint32_t d) { return d > 1 ? (uint32_t)((0x100000000ull + d - 1) / d) : 0u; };
     const uint32_t magic_w = magic_of(sw), magic_c = (sw & 1) ? 0u : magic_of(sw / 2);
-    size_t lds = (size_t)kWavesPerGroup * 64 * sdw * 4;
-    if (lds + sizeof(CoderTables) > 160 * 1024)  // the aligned kernels' static LDS: the coder tables
-      return fail("zfp_hip: block size %u bits too large for LDS", p.cp.maxbits);
+    const size_t lds = aligned_lds_bytes(p);
     Partial* parts = nullptr;
     if (g0) {
       if (!ensure(c->partials, nwaves * 2 * sizeof(Partial)))
@@ -625,7 +631,9 @@ static int launch_decode(Ctx* c, const Plan& p, S* d_field, const uint64_t* d_in
     return fail("zfp_hip: block index has %llu waves, the 3D layout needs %llu", (unsigned long long)index->nwaves,
                 (unsigned long long)nwaves);
   const uint64_t ngroups = (nwaves + kWavesPerGroup - 1) / kWavesPerGroup;
-  const uint32_t per_block = p.fixed ? p.cp.maxbits : p.max_len;
+  // what a block can code: the decoder reads no further (minbits or fixed-rate
+  // padding past it is skipped, not read), so the padding is not staged
+  const uint32_t per_block = p.bound_bits;
   const uint32_t W_full = (per_block + 63) / 64 + 1;  // peek64 at the budget end reads one word past it
   const uint32_t W_short = short_stage_words<S>(p);
   for (int attempt = 0; attempt < 2; attempt++) {
