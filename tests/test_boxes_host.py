@@ -14,7 +14,8 @@ import re
 import numpy as np
 import pytest
 
-from test_region_host import LIB_HIP, LIB_ZFP, SENTINEL, _exports, _job, _kernel_scratch
+from kdesc import _kernel_scratch
+from test_region_host import LIB_HIP, LIB_ZFP, SENTINEL, _exports, _job
 
 
 class Region(ctypes.Structure):

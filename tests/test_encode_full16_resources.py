@@ -12,7 +12,8 @@ import struct
 
 import pytest
 
-from test_kernel_symbols import LIB, MAGIC, _sections
+from kdesc import MAGIC, _kernel_scratch, _sections
+from test_kernel_symbols import LIB
 
 KERNEL = "_ZN7zfp_amd20encode3_aligned_fullIfLb1ELb1ELi16EEEvPKT_NS_8GeometryENS_11CodecParamsEPmjjj"
 
@@ -73,7 +74,6 @@ def test_f64_aligned_full_scratch_is_what_it_was():
     """encode3_aligned_full<double, VEC> stands at its 168-VGPR bound and spills: 260 bytes per lane
     with 16-byte loads, 252 without.  The float kernels' opening (tables requested ahead of the
     block loads) is not theirs: holding the table quads across the loads cost them 20-32 bytes more."""
-    from test_kernel_symbols import _kernel_scratch
     sc = {k: v for k, v in _kernel_scratch(open(LIB, "rb").read()).items()
           if k.startswith("_ZN7zfp_amd20encode3_aligned_fullId")}
     assert len(sc) == 2, sorted(sc)

@@ -343,6 +343,41 @@ def test_host_and_device_memory(hip, oracle, mode, param, region):
             assert got == _blocks(reg, None, SHAPE)
 
 
+def _strided_views(ext, dtype):
+    """[(name, big, view)]: views of extents `ext` inside sentinel-filled arrays
+    whose x stride is 2, whose y axis is reversed, and both."""
+    out = []
+    for name, xs, yrev in (("x stride 2", 2, False), ("y reversed", 1, True), ("x stride 2, y reversed", 2, True)):
+        g = GUARD[3 - len(ext):]
+        big = np.empty([n + 2 * k for n, k in zip(ext[:-1], g)] + [xs * ext[-1] + 2 * g[-1]], dtype=dtype)
+        big.view(np.uint8)[...] = SENTINEL
+        view = big[tuple(slice(k, k + n) for n, k in zip(ext[:-1], g)) + (slice(g[-1], g[-1] + xs * ext[-1], xs),)]
+        out.append((name, big, view[:, ::-1, :] if yrev else view))
+    return out
+
+
+@pytest.mark.parametrize("mode,param", [("rate", 8), ("precision", 20)])
+def test_host_destination_with_x_stride_and_negative_y_stride(hip, oracle, mode, param):
+    """A host destination whose rows are not contiguous or run backwards: the
+    region's elements land where the strides say and nothing else is written."""
+    shape = (9, 10, 13)  # partial blocks on every axis
+    region = [(2, 7), (1, 9), (3, 12)]
+    rng = np.random.default_rng(61)
+    a = _special_field(shape, np.float32, rng)
+    params = _params(mode, param, TYPE_FLOAT, 3)
+    words, _ = oracle.compress_words(a, params)
+    ref, _ = oracle.decompress_words(words, shape, np.float32, params)
+    want = ref[tuple(slice(lo, hi) for lo, hi in region)]
+    job = _job(shape, TYPE_FLOAT, params)
+    for name, big, view in _strided_views([hi - lo for lo, hi in region], np.float32):
+        got = _region_decode(hip, job, region, view.ctypes.data, [s // 4 for s in view.strides], words.ctypes.data,
+                             len(words))
+        assert np.ascontiguousarray(view).tobytes() == np.ascontiguousarray(want).tobytes(), (name, "values")
+        view[...] = np.frombuffer(bytes([SENTINEL] * 4), dtype=np.float32)[0]  # (an ordinary value: stored as it is)
+        assert (big.view(np.uint8) == SENTINEL).all(), (name, "bytes outside the region written")
+        assert got == _blocks(region, None, shape), (name, "blocks_read")
+
+
 def test_4d_is_refused(hip):
     shape = (8, 8, 8, 8)
     job = _job(shape, TYPE_FLOAT, params_rate(8, TYPE_FLOAT, 4))

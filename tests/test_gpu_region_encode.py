@@ -30,7 +30,8 @@ import pytest
 
 from pyoracle import TYPE_FLOAT, ZFP_MIN_EXP, params_rate
 
-from test_gpu_region import REGIONS, SHAPE, TYPES, _arr4, _blocks, _guarded, _int_field, _job, _special_field
+from test_gpu_region import (REGIONS, SHAPE, TYPES, _arr4, _blocks, _guarded, _int_field, _job, _special_field,
+                             _strided_views)
 
 pytestmark = pytest.mark.gpu
 
@@ -317,6 +318,31 @@ def test_host_and_device_memory(hip, oracle, region):
             assert (buf[:NSENT] == SENT).all() and (buf[-NSENT:] == SENT).all(), (dev_stream, dev_src)
             assert buf[NSENT:-NSENT].tobytes() == want.tobytes(), (dev_stream, dev_src)
             assert got == int((cls != 0).sum())
+
+
+def test_host_source_with_x_stride_and_negative_y_stride(hip, oracle):
+    """A host source whose rows are not contiguous or run backwards gives the
+    stream of a contiguous copy of the same values, word for word."""
+    shape = (9, 10, 13)  # partial blocks on every axis
+    region = [(2, 7), (1, 9), (3, 12)]
+    rng = np.random.default_rng(61)
+    a = _special_field(shape, np.float32, rng)
+    new = np.ascontiguousarray(_special_field(shape, np.float32, rng)[tuple(slice(lo, hi) for lo, hi in region)])
+    codec = _Codec(oracle, shape, np.float32, params_rate(8, TYPE_FLOAT, 3))
+    w_old = codec.compress(a)
+    job = _job(shape, TYPE_FLOAT, codec.params)
+
+    def encode(src):
+        w = w_old.copy()
+        got = _call(hip, job, region, src.ctypes.data, [s // 4 for s in src.strides], w.ctypes.data, len(w), 0)
+        assert got == _blocks(region, None, shape)
+        return w
+
+    want = encode(new)
+    assert want.tobytes() != w_old.tobytes()
+    for name, _, view in _strided_views(list(new.shape), np.float32):
+        view[...] = new
+        assert encode(view).tobytes() == want.tobytes(), name
 
 
 # 7. chained updates

@@ -4,22 +4,22 @@ Every validation failure of zfp_hip_decompress_region / zfp_decompress_region is
 decided before any GPU call, returns 0 and leaves the destination untouched, so
 these run on a machine without a GPU.  The float 3D lossy region kernel must
 keep its plane registers in VGPRs (private segment 0), as decode3<float> does;
-the descriptors are read from libzfp_hip.so as test_kernel_symbols.py reads them.
+the descriptors are read from libzfp_hip.so by kdesc.py.
 """
 import ctypes
 import os
 import re
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+from kdesc import _kernel_scratch
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.join(REPO, "zfp-par_amd", "lib")
 LIB_HIP = os.path.join(LIBDIR, "libzfp_hip.so")
 LIB_ZFP = os.path.join(LIBDIR, "libzfp.so")
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 SENTINEL = 0x5A
 
 
@@ -151,59 +151,6 @@ def test_host_api_refuses_type_and_extent_mismatches(prod):
         lib.zfp_field_free(field)
         lib.zfp_stream_close(zs)
         lib.stream_close(bs)
-
-
-# ---- kernel descriptors (the helpers of test_kernel_symbols.py) ----
-def _sections(elf):
-    """(name, type, offset, size, link) of every section of an ELF64 image."""
-    shoff, = struct.unpack_from("<Q", elf, 0x28)
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
-    hdrs = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
-    stro = hdrs[shstrndx][4]
-    out = []
-    for h in hdrs:
-        nm = elf[stro + h[0]: elf.index(b"\0", stro + h[0])].decode()
-        out.append((nm, h[1], h[4], h[5], h[6]))
-    return out
-
-
-def _kernel_scratch(lib_bytes):
-    """{kernel: private_segment_fixed_size} from the gfx950 kernel descriptors (.kd)."""
-    secs = {nm: (off, size) for nm, _, off, size, _ in _sections(lib_bytes)}
-    off, size = secs[".hip_fatbin"]
-    fb = lib_bytes[off: off + size]
-    out, i = {}, 0
-    while True:
-        j = fb.find(MAGIC, i)
-        if j < 0:
-            break
-        n, = struct.unpack_from("<Q", fb, j + 24)
-        p = j + 32
-        for _ in range(n):
-            o, sz, tl = struct.unpack_from("<QQQ", fb, p)
-            p += 24
-            triple = fb[p: p + tl].decode()
-            p += tl
-            if "gfx950" not in triple or not sz:
-                continue
-            elf = fb[j + o: j + o + sz]
-            shoff, = struct.unpack_from("<Q", elf, 0x28)
-            shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
-            hdrs = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + k * shentsize) for k in range(shnum)]
-            for h in hdrs:
-                if h[1] not in (2, 11):
-                    continue
-                stro = hdrs[h[6]][4]
-                for k in range(h[5] // 24):
-                    st_name, _, _, shndx, value, _ = struct.unpack_from("<IBBHQQ", elf, h[4] + k * 24)
-                    nm = elf[stro + st_name: elf.index(b"\0", stro + st_name)].decode() if st_name else ""
-                    if not nm.endswith(".kd") or shndx == 0 or shndx >= len(hdrs):
-                        continue
-                    sec = hdrs[shndx]
-                    kd = sec[4] + (value - sec[3])  # file offset of the descriptor
-                    out[nm[:-3]] = struct.unpack_from("<I", elf, kd + 4)[0]
-        i = j + len(MAGIC)
-    return out
 
 
 def test_float_3d_lossy_region_kernel_uses_no_scratch():

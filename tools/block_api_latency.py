@@ -4,7 +4,7 @@ zfp_decode_block_float_3) on this library, where each call is one GPU round
 trip, and of the bulk paths the GPU arrays use instead (one zfp_compress of a
 line of 256 blocks, one of a whole 129^3 array).
 
-usage: python tools/block_api_latency.py [--calls 2000]
+usage: python tools/block_api_latency.py [--calls 2000] [--lib path/to/libzfp.so]
 """
 import argparse
 import ctypes
@@ -21,9 +21,10 @@ sys.path[:0] = [os.path.join(R, "tests")]
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=2000)
+    ap.add_argument("--lib", default=os.path.join(R, "zfp-par_amd", "lib", "libzfp.so"))
     a = ap.parse_args()
     from capi import ZfpCAPI
-    api = ZfpCAPI(os.path.join(R, "zfp-par_amd", "lib", "libzfp.so"))
+    api = ZfpCAPI(a.lib)
     lib = api.lib
     for fn in ("zfp_encode_block_float_3", "zfp_decode_block_float_3"):
         getattr(lib, fn).restype = ctypes.c_size_t

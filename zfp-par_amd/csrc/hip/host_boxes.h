@@ -1,6 +1,6 @@
 // Host shim: batched region decode (zfp_hip_decompress_regions) -- validation
-// of every entry, the table of region records and wave_first, the one launch
-// and the copy-out of host destinations.
+// of every entry, and region_decode_once with the batch's destinations (the
+// table of region records and wave_first), its one launch and its copy-outs.
 #pragma once
 
 #include "host_region.h"
@@ -22,13 +22,9 @@ static int plan_regions(const zfp_hip_job* job, const zfp_hip_region* regions, u
   const char* who = "zfp_hip_decompress_regions";
   if (!job || !regions || !words)
     return fail("%s: null job, regions or stream pointer", who);
-  zfp_hip_job j = *job;  // (job->s is not used: every destination has its own strides)
-  for (int a = 0; a < 4; a++)
-    j.s[a] = 0;
-  if (!plan_job(&j, nullptr, p))
+  zfp_hip_job j;
+  if (!plan_coded_box(who, "decode", job, p, j))
     return 0;
-  if (p.dims == 4)
-    return fail("%s: 4D region decode is not supported (1D to 3D fields only)", who);
   if (nregions > kMaxRegions)
     return fail("%s: %llu regions in one call (at most %llu)", who, (unsigned long long)nregions,
                 (unsigned long long)kMaxRegions);
@@ -37,16 +33,16 @@ static int plan_regions(const zfp_hip_job* job, const zfp_hip_region* regions, u
   uint64_t waves = 0;
   for (uint64_t i = 0; i < nregions; i++) {
     const zfp_hip_region& r = regions[i];
+    char entry[96];  // a failing entry's name: written when one fails
+    auto named = [&](const char* colon) {
+      snprintf(entry, sizeof entry, "regions[%llu] (entry %llu of %llu)%s", (unsigned long long)i,
+               (unsigned long long)(i + 1), (unsigned long long)nregions, colon);
+      return entry;
+    };
     if (!r.dst)
-      return fail("%s: regions[%llu] (entry %llu of %llu) has a null destination", who, (unsigned long long)i,
-                  (unsigned long long)(i + 1), (unsigned long long)nregions);
-    for (int a = 0; a < p.dims; a++)
-      if (!(j.f[a] <= r.lo[a] && r.lo[a] < r.hi[a] && r.hi[a] <= j.e[a]))
-        return fail("%s: regions[%llu] (entry %llu of %llu): region [%llu, %llu) on axis %d is empty or not inside "
-                    "the coded box [%llu, %llu)",
-                    who, (unsigned long long)i, (unsigned long long)(i + 1), (unsigned long long)nregions,
-                    (unsigned long long)r.lo[a], (unsigned long long)r.hi[a], a, (unsigned long long)j.f[a],
-                    (unsigned long long)j.e[a]);
+      return fail("%s: %s has a null destination", who, named(""));
+    if (!check_region_box(who, "", j, p.dims, r.lo, r.hi))  // (failed: once more, for the message with the entry)
+      return check_region_box(who, named(": "), j, p.dims, r.lo, r.hi);
     RegionGeom& rg = bp.rec[i].rg;
     rg = make_region_geom(p.g, p.dims, r.lo, r.hi, r.dst_stride);
     bp.rec[i].dst = r.dst;
@@ -61,12 +57,10 @@ static int plan_regions(const zfp_hip_job* job, const zfp_hip_region* regions, u
   return 1;
 }
 
-// One batched decode with the given index (nullptr: the stream is scanned);
-// *stale and *scanned as decompress_once.  `bp.rec` holds the caller's
-// destinations and strides and is left as it is.
+// One batched decode; `bp.rec` holds the caller's destinations and strides
+// and is left as it is, `rec` is the table as the kernel reads it.
 static int regions_once(Ctx* c, const Plan& p, const BoxesPlan& bp, std::vector<BoxRecord>& rec,
-                        const zfp_hip_region* regions, const uint64_t* words, uint64_t capacity_words,
-                        uint64_t bit_offset, const zfp_hip_index* index, bool plain_scan, bool* stale, bool* scanned)
+                        const zfp_hip_region* regions, const DecodeTry& t)
 {
   const size_t n = bp.rec.size();
   bool dev_dst = false;
@@ -86,58 +80,48 @@ static int regions_once(Ctx* c, const Plan& p, const BoxesPlan& bp, std::vector<
     Blo = std::min(Blo, lo);
     Bhi = std::max(Bhi, hi);
   }
-  RegionArgs a;
-  size_t lds;
-  if (!region_stream(c, p, Blo, Bhi, words, capacity_words, bit_offset, index, plain_scan, scanned, a, &lds))
-    return 0;
-  // destinations: the caller's device arrays, or dense images of the regions
-  // back to back in the field scratch, each from a 16-byte boundary on
-  rec = bp.rec;
-  std::vector<size_t> img;
-  if (!dev_dst) {
-    img.resize(n);
-    size_t bytes = 0;
-    for (size_t i = 0; i < n; i++) {
-      RegionGeom& rg = rec[i].rg;
-      uint64_t count = 1;
-      for (int k = 0; k < p.dims; k++) {
-        rg.ds[k] = (int64_t)count;
-        count *= rg.hi[k] - rg.lo[k];
-      }
-      img[i] = bytes;
-      bytes += ((size_t)count * p.es + 15) & ~(size_t)15;
-    }
-    if (!ensure(c->field, bytes))
-      return 0;
-    for (size_t i = 0; i < n; i++)
-      rec[i].dst = (char*)c->field.p + img[i];
-  }
-  for (size_t i = 0; i < n; i++)
-    rec[i].rg.vec = region_vec_ok(rec[i].rg, p.dims, rec[i].dst) ? 1u : 0u;
-  // the table: the records, then wave_first
   const size_t rec_bytes = n * sizeof(BoxRecord), wf_bytes = (n + 1) * sizeof(uint32_t);
-  if (!ensure(c->boxes, rec_bytes + wf_bytes))
-    return 0;
-  if (!h2d(c, c->boxes.p, rec.data(), rec_bytes, c->stream) ||
-      !h2d(c, (char*)c->boxes.p + rec_bytes, bp.wave_first.data(), wf_bytes, c->stream))
-    return 0;
-  BoxesArgs b;
-  b.rec = (const BoxRecord*)c->boxes.p;
-  b.wave_first = (const uint32_t*)((const char*)c->boxes.p + rec_bytes);
-  b.n = (uint32_t)n;
-  const uint64_t waves = bp.wave_first[n];
-  const dim3 grid((unsigned)((waves + kWavesPerGroup - 1) / kWavesPerGroup));
-  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-  launch_decode_boxes(p.type, p.dims, p.cp.minexp < kMinExp, hi_planes<double>(p) && p.type == 4, c->stream, grid,
-                      lds, b, p.g, p.cp, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-  const uint32_t* pchk;
-  if (!region_queue_check(c, &pchk))
-    return 0;
-  if (!dev_dst)
-    for (size_t i = 0; i < n; i++)
-      if (!region_to_host(c, p, rec[i].rg, regions[i].dst_stride, regions[i].dst, rec[i].dst))
-        return 0;
-  return region_finish(c, pchk, stale);
+  return region_decode_once(
+      c, p, t, Blo, Bhi,
+      [&] {
+        // destinations: the caller's device arrays, or dense images of the regions
+        // back to back in the field scratch, each from a 16-byte boundary on
+        rec = bp.rec;
+        if (!dev_dst) {
+          std::vector<size_t> img(n);
+          size_t bytes = 0;
+          for (size_t i = 0; i < n; i++) {
+            img[i] = bytes;
+            bytes += (dense_image(rec[i].rg, p.dims, p.es) + 15) & ~(size_t)15;
+          }
+          if (!ensure(c->field, bytes))
+            return 0;
+          for (size_t i = 0; i < n; i++)
+            rec[i].dst = (char*)c->field.p + img[i];
+        }
+        for (size_t i = 0; i < n; i++)
+          rec[i].rg.vec = region_vec_ok(rec[i].rg, p.dims, rec[i].dst) ? 1u : 0u;
+        // the table: the records, then wave_first
+        if (!ensure(c->boxes, rec_bytes + wf_bytes) || !h2d(c, c->boxes.p, rec.data(), rec_bytes, c->stream) ||
+            !h2d(c, (char*)c->boxes.p + rec_bytes, bp.wave_first.data(), wf_bytes, c->stream))
+          return 0;
+        return 1;
+      },
+      [&](const RegionArgs& a, size_t lds) {
+        BoxesArgs b;
+        b.rec = (const BoxRecord*)c->boxes.p;
+        b.wave_first = (const uint32_t*)((const char*)c->boxes.p + rec_bytes);
+        b.n = (uint32_t)n;
+        const uint64_t waves = bp.wave_first[n];
+        const dim3 grid((unsigned)((waves + kWavesPerGroup - 1) / kWavesPerGroup));
+        launch_decode_boxes(p.type, p.dims, p.cp.minexp < kMinExp, hi_planes<double>(p) && p.type == 4, c->stream, grid,
+                            lds, b, p.g, p.cp, a);
+      },
+      [&] {
+        if (!dev_dst)
+          for (size_t i = 0; i < n; i++)
+            if (!region_to_host(c, p, rec[i].rg, regions[i].dst_stride, regions[i].dst, rec[i].dst))
+              return 0;
+        return 1;
+      });
 }

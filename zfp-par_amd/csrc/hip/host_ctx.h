@@ -183,7 +183,7 @@ static void release_ctx(Ctx* c)
   g_idle.push_back(c);
 }
 
-// Borrows a context for the lifetime of one API call (begin_call), and is the
+// Borrows a context for the lifetime of one API call (open_call), and is the
 // one place where a call's use of it ends.  An entry point returns through
 // done(rc): every successful call has synchronized the streams it queued work
 // on after queueing the last of it.  Any other way out -- a failed validation

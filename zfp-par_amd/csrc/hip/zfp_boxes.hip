@@ -1,58 +1,24 @@
 // Batched region decode kernels (kernels_boxes.h): the instantiations of
-// zfp_region.hip -- float and double 3D through decode_block3 (double also with
-// planes 32..63 only), 1D/2D of every scalar type and 3D integers through
-// decode_block_n.
+// zfp_region.hip (region_dispatch.h) -- float and double 3D through
+// decode_block3 (double also with planes 32..63 only), 1D/2D of every scalar
+// type and 3D integers through decode_block_n.
 #include "kernels_boxes.h"
+#include "region_dispatch.h"
 
 namespace zfp_amd {
-
-namespace {
-
-struct BoxesLaunch {
-  hipStream_t stream;
-  dim3 grid;
-  size_t lds;
-  const BoxesArgs& b;
-  const Geometry& g;
-  const CodecParams& cp;
-  const RegionArgs& a;
-};
-
-template <typename S, bool HI, int D>
-void boxes_kernel(const BoxesLaunch& l, bool rev)
-{
-  if (rev)
-    hipLaunchKernelGGL((decode3_boxes<S, true, HI, D>), l.grid, dim3(256), l.lds, l.stream, l.b, l.g, l.cp, l.a);
-  else
-    hipLaunchKernelGGL((decode3_boxes<S, false, HI, D>), l.grid, dim3(256), l.lds, l.stream, l.b, l.g, l.cp, l.a);
-}
-
-template <typename S>
-void boxes_by_dims(const BoxesLaunch& l, int dims, bool rev, bool hi)
-{
-  if (dims == 1)
-    return boxes_kernel<S, false, 1>(l, rev);
-  if (dims == 2)
-    return boxes_kernel<S, false, 2>(l, rev);
-  if constexpr (std::is_same<S, double>::value) {
-    if (hi)
-      return boxes_kernel<S, true, 3>(l, rev);
-  }
-  boxes_kernel<S, false, 3>(l, rev);
-}
-
-}  // namespace
 
 void launch_decode_boxes(int type, int dims, bool rev, bool hi, hipStream_t stream, dim3 grid, size_t lds,
                          const BoxesArgs& b, const Geometry& g, const CodecParams& cp, const RegionArgs& a)
 {
-  const BoxesLaunch l{stream, grid, lds, b, g, cp, a};
-  switch (type) {
-    case 1: return boxes_by_dims<int32_t>(l, dims, rev, hi);
-    case 2: return boxes_by_dims<int64_t>(l, dims, rev, hi);
-    case 3: return boxes_by_dims<float>(l, dims, rev, hi);
-    default: return boxes_by_dims<double>(l, dims, rev, hi);
-  }
+  by_region_kernel(type, dims, hi, [&](auto tag, auto hi_tag, auto dims_tag) {
+    using S = std::remove_pointer_t<decltype(tag)>;
+    constexpr bool HI = decltype(hi_tag)::value;
+    constexpr int D = decltype(dims_tag)::value;
+    if (rev)
+      hipLaunchKernelGGL((decode3_boxes<S, true, HI, D>), grid, dim3(256), lds, stream, b, g, cp, a);
+    else
+      hipLaunchKernelGGL((decode3_boxes<S, false, HI, D>), grid, dim3(256), lds, stream, b, g, cp, a);
+  });
 }
 
 }  // namespace zfp_amd

@@ -20,12 +20,14 @@
 #include "host_error.h"        // the per-thread error message, HIP_TRY
 #include "host_index.h"        // zfp_hip_index and its device storage
 #include "host_ctx.h"          // contexts, their pool, the per-call lease, pinned staging
+#include "host_call.h"         // how a call opens, the index check word, the stale-index retries
 #include "host_plan.h"         // Plan: what a job asks for
 #include "host_index_match.h"  // an index and the stream it describes
 #include "host_launch.h"       // encode and decode launchers
 #include "host_scan.h"         // index scan of a stream without an index
 #include "host_pipeline.h"     // host <-> device box copies, the slab pipeline
-#include "host_region.h"       // region decode: validation, start table, launch, copy-out
+#include "host_rows.h"         // rows of a strided host array <-> a packed image (no HIP call)
+#include "host_region.h"       // region decode, and the host pieces every region call shares
 #include "host_region_enc.h"   // region encode: validation, source image, launch, copy-back
 #include "host_boxes.h"        // batched region decode: validation, the region table, launch, copy-out
 
@@ -43,13 +45,7 @@ static int begin_call(CtxLease& lease, const char* who, const zfp_hip_job* job, 
     return fail("%s: null %s", who, null_arg);
   if (index_call && p.fixed)
     return fail("%s: fixed-rate streams need no index", who);
-  if (zfp_hip_device_count() <= 0)
-    return fail("%s: no HIP device available", who);
-  lease.c = acquire_ctx(device);
-  if (!lease.c)
-    return 0;
-  t_timing = Timing{};
-  return 1;
+  return open_call(lease, who, device);
 }
 
 extern "C" {
@@ -199,33 +195,9 @@ static int decompress_once(Ctx* c, const Plan& p, const zfp_hip_job* job, void* 
   const bool have_index = !p.fixed && index_matches(c, index, p, words, dev_stream, capacity_words, bit_offset);
   const bool scan = !p.fixed && !have_index;
   *scanned = scan;
-  // every variable-rate index is verified exactly by the decode kernels, every
-  // block's decoded length against its entry: a caller's that passed the
-  // (sampled) fingerprint, and the scan's own (its plausible-start heuristic
-  // and refusals must never decode garbage silently)
-  c->idx_chk = nullptr;
-  if (!p.fixed) {
-    if (!ensure(c->chk, 8))
-      return 0;
-    HIP_TRY(hipMemsetAsync(c->chk.p, 0, 4, c->stream));
-    c->idx_chk = (uint32_t*)c->chk.p;
-  }
-  const uint32_t* pchk = nullptr;  // the check word, fetched with the call's last synchronize
-  auto verified = [&]() -> int {
-    if (!c->idx_chk)
-      return 1;
-    uint32_t bad = 0;
-    c->idx_chk = nullptr;
-    if (pchk) {
-      bad = *pchk;
-    } else {
-      HIP_TRY(hipMemcpyAsync(&bad, c->chk.p, 4, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    if (bad)
-      *stale = true;
-    return 1;
-  };
+  CheckWord chk{c};  // (a variable-rate index is verified by the decode kernels: host_call.h)
+  if (!chk.arm(p.fixed))
+    return 0;
   const uint64_t nwords = at.decode_words(p.fixed      ? p.g.nblocks * (uint64_t)p.cp.maxbits
                                           : have_index ? index->total_bits
                                                        : p.g.nblocks * (uint64_t)p.max_len);
@@ -238,7 +210,7 @@ static int decompress_once(Ctx* c, const Plan& p, const zfp_hip_job* job, void* 
           return decompress_slabs<S>(c, p, sl, field_base, words, capacity_words, bit_offset, index, end_bit);
         });
       });
-      return ok ? verified() : 0;
+      return ok ? chk.verdict(stale) : 0;
     }
   }
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -270,20 +242,15 @@ static int decompress_once(Ctx* c, const Plan& p, const zfp_hip_job* job, void* 
   });
   if (!ok)
     return 0;
-  if (c->idx_chk) {
-    uint32_t* q = (uint32_t*)pin_take(c, 4);
-    if (q) {
-      HIP_TRY(hipMemcpyAsync(q, c->chk.p, 4, hipMemcpyDeviceToHost, c->stream));
-      pchk = q;
-    }
-  }
+  if (!chk.queue())
+    return 0;
   if (!dev_field && !copy_box(c, p, field_base, d_img, p.es, true))
     return 0;
   HIP_TRY(hipEventRecord(c->ev[3], c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   record_timing(c);
   *end_bit = bit_offset + total;
-  return verified();
+  return chk.verdict(stale);
 }
 
 int zfp_hip_decompress(const zfp_hip_job* job, void* field_base, const uint64_t* words, uint64_t capacity_words,
@@ -299,62 +266,31 @@ int zfp_hip_decompress(const zfp_hip_job* job, void* field_base, const uint64_t*
     *end_bit = bit_offset;
     return lease.done(1);
   }
-  bool stale = false, scanned = false;
-  auto once = [&](const zfp_hip_index* x, bool plain) {
-    stale = false;
-    return decompress_once(c, p, job, field_base, words, capacity_words, bit_offset, x, end_bit, plain, &stale,
-                           &scanned);
-  };
-  int ok = once(index, false);
-  if (ok && stale) {
-    // the index failed the block lengths: a caller's index (it passed the
-    // fingerprint) is replaced by the scan's; a scan-built one by a scan of
-    // plain passes (no plausible starts, no refusals)
-    const bool plain = scanned;
-    ok = once(nullptr, plain);
-    if (ok && stale && !plain)
-      ok = once(nullptr, true);
-    t_timing.stale_index = true;
-    if (ok && stale)
-      return fail("zfp_hip_decompress: decoded block lengths disagree with the stream's plain scan (corrupt stream)");
-  }
+  const int ok = with_stale_retry("zfp_hip_decompress", index,
+                                  [&](const zfp_hip_index* x, bool plain, bool* stale, bool* scanned) {
+                                    return decompress_once(c, p, job, field_base, words, capacity_words, bit_offset, x,
+                                                           end_bit, plain, stale, scanned);
+                                  });
   return lease.done(ok);
 }
 
+// (The region entries do not go through begin_call: the job's strides are
+// unused, and everything is validated before the first GPU call, the device
+// count included.)
 int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], const uint64_t hi[4], void* dst,
                               const int64_t dst_stride[4], const uint64_t* words, uint64_t capacity_words,
                               uint64_t bit_offset, int device, const zfp_hip_index* index, uint64_t* blocks_read)
 {
-  // (not begin_call: the job's strides are unused and everything is validated
-  // before the first GPU call, the device count included)
+  const char* who = "zfp_hip_decompress_region";
   Plan p;
   RegionGeom rg;
-  if (!plan_region(job, lo, hi, dst, dst_stride, words, p, rg))
-    return 0;
-  if (zfp_hip_device_count() <= 0)
-    return fail("zfp_hip_decompress_region: no HIP device available");
   CtxLease lease;
-  lease.c = acquire_ctx(device);
-  if (!lease.c)
+  if (!plan_region(job, lo, hi, dst, dst_stride, words, p, rg) || !open_call(lease, who, device))
     return 0;
-  Ctx* c = lease.c;
-  t_timing = Timing{};
-  bool stale = false, scanned = false;
-  auto once = [&](const zfp_hip_index* x, bool plain) {
-    stale = false;
-    return region_once(c, p, rg, dst, dst_stride, words, capacity_words, bit_offset, x, plain, &stale, &scanned);
-  };
-  int ok = once(index, false);
-  if (ok && stale) {  // as zfp_hip_decompress: scan, then a scan of plain passes
-    const bool plain = scanned;
-    ok = once(nullptr, plain);
-    if (ok && stale && !plain)
-      ok = once(nullptr, true);
-    t_timing.stale_index = true;
-    if (ok && stale)
-      return fail("zfp_hip_decompress_region: decoded block lengths disagree with the stream's plain scan "
-                  "(corrupt stream)");
-  }
+  const int ok = with_stale_retry(who, index, [&](const zfp_hip_index* x, bool plain, bool* stale, bool* scanned) {
+    return region_once(lease.c, p, rg, dst, dst_stride,
+                       DecodeTry{words, capacity_words, bit_offset, x, plain, stale, scanned});
+  });
   if (ok && blocks_read)
     *blocks_read = rg.nrblocks;
   return lease.done(ok);
@@ -364,7 +300,7 @@ int zfp_hip_decompress_regions(const zfp_hip_job* job, const zfp_hip_region* reg
                                const uint64_t* words, uint64_t capacity_words, uint64_t bit_offset, int device,
                                const zfp_hip_index* index, uint64_t* blocks_read)
 {
-  // (as zfp_hip_decompress_region: everything is validated before the first GPU call)
+  const char* who = "zfp_hip_decompress_regions";
   Plan p;
   BoxesPlan bp;
   std::vector<BoxRecord> rec;  // (outlives the lease: it may have to wait for the table's copy)
@@ -375,30 +311,14 @@ int zfp_hip_decompress_regions(const zfp_hip_job* job, const zfp_hip_region* reg
       *blocks_read = 0;
     return 1;
   }
-  if (zfp_hip_device_count() <= 0)
-    return fail("zfp_hip_decompress_regions: no HIP device available");
   CtxLease lease;
-  lease.c = acquire_ctx(device);
-  if (!lease.c)
+  if (!open_call(lease, who, device))
     return 0;
-  Ctx* c = lease.c;
-  t_timing = Timing{};
-  bool stale = false, scanned = false;
-  auto once = [&](const zfp_hip_index* x, bool plain) {
-    stale = false;
-    return regions_once(c, p, bp, rec, regions, words, capacity_words, bit_offset, x, plain, &stale, &scanned);
-  };
-  int ok = once(index, false);
-  if (ok && stale) {  // as zfp_hip_decompress: the whole batch again with the scan, then a scan of plain passes
-    const bool plain = scanned;
-    ok = once(nullptr, plain);
-    if (ok && stale && !plain)
-      ok = once(nullptr, true);
-    t_timing.stale_index = true;
-    if (ok && stale)
-      return fail("zfp_hip_decompress_regions: decoded block lengths disagree with the stream's plain scan "
-                  "(corrupt stream)");
-  }
+  // (a stale index repeats the whole batch)
+  const int ok = with_stale_retry(who, index, [&](const zfp_hip_index* x, bool plain, bool* stale, bool* scanned) {
+    return regions_once(lease.c, p, bp, rec, regions,
+                        DecodeTry{words, capacity_words, bit_offset, x, plain, stale, scanned});
+  });
   if (ok && blocks_read)
     *blocks_read = bp.blocks;
   return lease.done(ok);
@@ -408,18 +328,12 @@ int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const 
                             const int64_t src_stride[4], uint64_t* words, uint64_t capacity_words,
                             uint64_t bit_offset, int device, uint64_t* blocks_written)
 {
-  // (as zfp_hip_decompress_region: everything is validated before the first GPU call)
   Plan p;
   RegionGeom rg;
-  if (!plan_region_enc(job, lo, hi, src, src_stride, words, capacity_words, bit_offset, p, rg))
-    return 0;
-  if (zfp_hip_device_count() <= 0)
-    return fail("zfp_hip_compress_region: no HIP device available");
   CtxLease lease;
-  lease.c = acquire_ctx(device);
-  if (!lease.c)
+  if (!plan_region_enc(job, lo, hi, src, src_stride, words, capacity_words, bit_offset, p, rg) ||
+      !open_call(lease, "zfp_hip_compress_region", device))
     return 0;
-  t_timing = Timing{};
   const int ok = region_enc_once(lease.c, p, rg, src, src_stride, words, capacity_words, bit_offset);
   if (ok && blocks_written)
     *blocks_written = rg.nrblocks;

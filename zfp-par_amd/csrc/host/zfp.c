@@ -1197,6 +1197,25 @@ static void whole_chunk(zfp_chunk* whole, const zfp_field* field)
   whole->ew = field->nw;
 }
 
+/* What the region entries share once their pairs are checked: the job of the
+ * coded box (NULL: the whole field) and, for a variable-rate stream, its
+ * attached index. */
+static zfp_hip_index* region_job(zfp_hip_job* job, const zfp_stream* zfp, const zfp_field* field,
+                                 const zfp_chunk* coded)
+{
+  zfp_chunk whole;
+  if (!coded) {
+    whole_chunk(&whole, field);
+    coded = &whole;
+  }
+  job_from(job, zfp, coded, field);
+  if (variable_rate(zfp, field)) {
+    ext_entry* x = ext_find(zfp, 0);
+    return x ? x->index : NULL;
+  }
+  return NULL;
+}
+
 /* Region decode (no reference equivalent): the blocks of `coded` that intersect
  * `region`, written into `out` -- zfp_hip_decompress_region with the stream's
  * attached index, its device and its bit position, which stays where it is. */
@@ -1205,8 +1224,7 @@ zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zf
 {
   bitstream* s;
   zfp_hip_job job;
-  zfp_chunk whole;
-  zfp_hip_index* index = NULL;
+  zfp_hip_index* index;
   uint64 lo[4], hi[4];
   int64_t ds[4];
   if (!zfp || !zfp->stream || !field)
@@ -1214,15 +1232,7 @@ zfp_bool zfp_decompress_region(zfp_stream* zfp, const zfp_field* field, const zf
   s = zfp->stream;
   if (!region_pair(field, zfp_field_dimensionality(field), region, out, lo, hi, ds))
     return zfp_false;
-  if (!coded) {
-    whole_chunk(&whole, field);
-    coded = &whole;
-  }
-  job_from(&job, zfp, coded, field);
-  if (variable_rate(zfp, field)) {
-    ext_entry* x = ext_find(zfp, 0);
-    index = x ? x->index : NULL;
-  }
+  index = region_job(&job, zfp, field, coded);
   if (!zfp_hip_decompress_region(&job, lo, hi, out->data, ds, s->begin, (uint64)(s->end - s->begin), stream_rtell(s),
                                  stream_device(zfp), index, NULL)) {
     report("zfp_decompress_region");
@@ -1239,8 +1249,7 @@ zfp_bool zfp_decompress_regions(zfp_stream* zfp, const zfp_field* field, const z
 {
   bitstream* s;
   zfp_hip_job job;
-  zfp_chunk whole;
-  zfp_hip_index* index = NULL;
+  zfp_hip_index* index;
   zfp_hip_region* r;
   zfp_bool ok = zfp_true;
   uint d;
@@ -1257,15 +1266,7 @@ zfp_bool zfp_decompress_regions(zfp_stream* zfp, const zfp_field* field, const z
       r[i].dst = outs[i]->data;
   }
   if (ok) {
-    if (!coded) {
-      whole_chunk(&whole, field);
-      coded = &whole;
-    }
-    job_from(&job, zfp, coded, field);
-    if (variable_rate(zfp, field)) {
-      ext_entry* x = ext_find(zfp, 0);
-      index = x ? x->index : NULL;
-    }
+    index = region_job(&job, zfp, field, coded);
     if (!zfp_hip_decompress_regions(&job, r, nregions, s->begin, (uint64)(s->end - s->begin), stream_rtell(s),
                                     stream_device(zfp), index, NULL)) {
       report("zfp_decompress_regions");
@@ -1289,41 +1290,16 @@ zfp_bool zfp_compress_region(zfp_stream* zfp, const zfp_field* field, const zfp_
 {
   bitstream* s;
   zfp_hip_job job;
-  zfp_chunk whole;
-  ptrdiff_t st[4];
   uint64 lo[4], hi[4];
   int64_t ss[4];
-  uint d;
-  if (!zfp || !zfp->stream || !field || !region || !in || !in->data)
+  if (!zfp || !zfp->stream || !field)
     return zfp_false;
   s = zfp->stream;
-  d = zfp_field_dimensionality(field);
-  if (field->type != in->type || zfp_field_dimensionality(in) != d)
-    return zfp_false;
   if (variable_rate(zfp, field))
     return zfp_false;
-  if (!coded) {
-    whole.fx = whole.fy = whole.fz = whole.fw = 0;
-    whole.ex = field->nx;
-    whole.ey = field->ny;
-    whole.ez = field->nz;
-    whole.ew = field->nw;
-    coded = &whole;
-  }
-  {
-    const size_t f[4] = {region->fx, region->fy, region->fz, region->fw};
-    const size_t e[4] = {region->ex, region->ey, region->ez, region->ew};
-    const size_t n[4] = {in->nx, in->ny, in->nz, in->nw};
-    field_strides(in, st);
-    for (uint a = 0; a < 4; a++) {
-      lo[a] = a < d ? f[a] : 0;
-      hi[a] = a < d ? e[a] : 0;
-      ss[a] = a < d ? (int64_t)st[a] : 0;
-      if (a < d && (e[a] <= f[a] || e[a] - f[a] != n[a]))
-        return zfp_false;
-    }
-  }
-  job_from(&job, zfp, coded, field);
+  if (!region_pair(field, zfp_field_dimensionality(field), region, in, lo, hi, ss))
+    return zfp_false;
+  (void)region_job(&job, zfp, field, coded); /* (fixed rate: no index) */
   if (!zfp_hip_compress_region(&job, lo, hi, in->data, ss, s->begin, (uint64)(s->end - s->begin), stream_wtell(s),
                                stream_device(zfp), NULL)) {
     report("zfp_compress_region");
