@@ -26,8 +26,17 @@
  *
  * Memory: `field_base` and `words` may each be host or device (hipMalloc)
  * memory; the library stages host buffers through device memory itself.
- * Threading: distinct calls may run concurrently from different host threads
- * (each thread gets its own HIP stream and scratch); one call is not reentrant.
+ * Threading: distinct calls may run concurrently from different host threads.
+ * Each call (not each thread) borrows a context -- a HIP stream and scratch --
+ * from a process-wide pool and returns it when it ends, so consecutive calls of
+ * one thread usually reuse one context and concurrent calls never share one.
+ * Concurrent calls may share what they only read: a stream being decoded, a
+ * field being encoded, and an index (the start table a region decode makes
+ * from it is built once, under a lock).  What a call writes -- the destination
+ * field, the stream or index an encode fills -- belongs to that call alone;
+ * in particular two region encodes on one stream at the same time are not
+ * supported.  The last-error, last-timing, last-scan and stale-index queries
+ * answer for the calling thread's most recent call, a refused one included.
  * Errors: entry points return 0 on failure (unsupported type/dimensionality,
  * capacity too small, HIP error); zfp_hip_last_error() describes the failure.
  */

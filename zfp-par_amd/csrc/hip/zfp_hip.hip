@@ -39,6 +39,7 @@
 static int begin_call(CtxLease& lease, const char* who, const zfp_hip_job* job, const void* field_base,
                       const char* null_arg, bool index_call, int device, Plan& p)
 {
+  t_timing = Timing{};  // a call refused below is still this thread's most recent call
   if (!plan_job(job, field_base, p))
     return 0;
   if (null_arg)
@@ -285,6 +286,7 @@ int zfp_hip_decompress_region(const zfp_hip_job* job, const uint64_t lo[4], cons
   Plan p;
   RegionGeom rg;
   CtxLease lease;
+  t_timing = Timing{};  // (as begin_call: a region refused before open_call reports no scan, no timing)
   if (!plan_region(job, lo, hi, dst, dst_stride, words, p, rg) || !open_call(lease, who, device))
     return 0;
   const int ok = with_stale_retry(who, index, [&](const zfp_hip_index* x, bool plain, bool* stale, bool* scanned) {
@@ -304,6 +306,7 @@ int zfp_hip_decompress_regions(const zfp_hip_job* job, const zfp_hip_region* reg
   Plan p;
   BoxesPlan bp;
   std::vector<BoxRecord> rec;  // (outlives the lease: it may have to wait for the table's copy)
+  t_timing = Timing{};
   if (!plan_regions(job, regions, nregions, words, p, bp))
     return 0;
   if (nregions == 0) {
@@ -331,6 +334,7 @@ int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const 
   Plan p;
   RegionGeom rg;
   CtxLease lease;
+  t_timing = Timing{};
   if (!plan_region_enc(job, lo, hi, src, src_stride, words, capacity_words, bit_offset, p, rg) ||
       !open_call(lease, "zfp_hip_compress_region", device))
     return 0;
