@@ -324,6 +324,16 @@ zfp_bool zfp_decompress_regions(zfp_stream* stream, const zfp_field* field, cons
  * 1D to 3D fields. */
 zfp_bool zfp_compress_region(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
                              const zfp_chunk* region, const zfp_field* in);
+/* MI355X addition: batched region encode, the write twin of zfp_decompress_regions.
+ * `nregions` regions of one fixed-rate stream rewritten in one GPU launch: every (regions[i], ins[i]) pair
+ * follows the contract of zfp_compress_region (ins[i] has the region's type, dimensionality and extents, with
+ * its own pointer and strides; host or device memory, all of one kind).  No 4^d block of the coded box (blocks
+ * count from its origin) may intersect two regions: such a batch is refused.  The stream is positioned for
+ * writing at the first block; its position (stream_wtell) is left unchanged and bits pending in the bitstream's
+ * buffer are kept.  zfp_false, with nothing written, for a variable-rate stream, a mismatch in any pair and two
+ * regions that share a block. */
+zfp_bool zfp_compress_regions(zfp_stream* stream, const zfp_field* field, const zfp_chunk* coded,
+                              const zfp_chunk* regions, size_t nregions, const zfp_field* const* ins);
 /* zfp.h:797-838: dispatch with an explicit execution policy, strided flag,
  * dimensionality and scalar type (zfp_compress_chunk derives them) */
 size_t zfp_compress_call(zfp_stream* stream, const zfp_chunk* chunk, const zfp_field* field, const uint exec,

@@ -208,6 +208,59 @@ int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const 
                             uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
                             int device, uint64_t* blocks_written);
 
+/* One region of a batch (zfp_hip_compress_regions). */
+typedef struct zfp_hip_src_region {
+  uint64_t lo[4], hi[4];    /* as zfp_hip_compress_region */
+  const void* src;          /* host or device memory */
+  int64_t src_stride[4];    /* element strides */
+} zfp_hip_src_region;
+
+/*
+ * Batched region encode: `nregions` sub-boxes of the coded box of `job`, each
+ * from its own source, rewritten in place in one kernel launch (the regions'
+ * blocks are dealt out to the launch's waves, whole waves per region).  After
+ * the call the stream holds what one zfp_hip_compress_region call per entry,
+ * in any order, would leave: every block that intersects a region holds the
+ * bits zfp_hip_compress writes for it from the image (a full decode of the
+ * old stream with that region's elements replaced); covered blocks are coded
+ * from the source alone, partly covered ones are decoded, overlaid and coded
+ * again; every other bit is untouched -- other blocks, bits below
+ * `bit_offset`, bits past the last block, words past the stream.
+ * The block sets of the entries must be pairwise disjoint: two entries that
+ * intersect a common 4^d block (blocks count from the coded box's origin) are
+ * refused, with a message that names both, even if their elements are
+ * disjoint.  The merge into the stream relies on no block's bits being read
+ * by any wave but its own, before that wave's writes; that holds across
+ * regions exactly when no block belongs to two of them.  A shared block would
+ * be read by one wave while another rewrites it, and the result would depend
+ * on the entries' order.  Blocks of different entries that share a stream
+ * word (rate 3.25, a 96-bit header) are fine.  A caller with adjacent tiles
+ * that do not lie on multiples of 4 from the coded box's origin merges them
+ * or makes two calls.
+ * These return 0 before any GPU call, with the stream and *blocks_written
+ * untouched: a null `job`, `regions` or `words`, a null `src` in any entry,
+ * any entry's region empty or outside the coded box (the message names the
+ * entry), a 4D job, a variable-rate job, more than 65,536 regions, more than
+ * 2^32 - 1 lanes once every region is padded to whole waves of 64 blocks, a
+ * stream whose `capacity_words` ends before the last bit of the highest block
+ * any entry needs, and two entries that share a block.  One bad entry fails
+ * the whole call.  nregions == 0 returns 1 with *blocks_written = 0 and makes
+ * no GPU call.  The sources are all in host or all in device memory; a
+ * mixture returns 0 before any launch or copy.
+ * Host `words`: one span is staged, from the first word of the lowest block
+ * any region needs to the last word of the highest, merged on the device and
+ * copied back whole -- for regions that lie far apart that is most of the
+ * stream; streams in device memory are the fast path.  Host sources are
+ * packed into dense device images.  Two calls on one stream at the same time
+ * are not supported.
+ * *blocks_written (optional) receives the sum over the entries of
+ * zfp_hip_compress_region's block count (padding lanes are not counted).
+ * zfp_hip_last_timing reports the one launch.
+ */
+int zfp_hip_compress_regions(const zfp_hip_job* job, const zfp_hip_src_region* regions, uint64_t nregions,
+                             uint64_t* words, uint64_t capacity_words, uint64_t bit_offset,
+                             int device, uint64_t* blocks_written);
+
 /*
  * Build the block index of the variable-rate stream at `words` for the chunk
  * box of `job`, blocks starting at bit `bit_offset` (a parallel parse of the

@@ -140,34 +140,24 @@ struct RegionEncArgs {
   uint32_t wmagic;  // ceil(2^32 / W)
 };
 
-// HI: double with maxprec <= 32.  D: block dimensionality; 1D/2D blocks and
-// integer fields take the generic per-lane codec (blockn.h).
+// One wave's share of a region: its 64 region blocks from `first` on
+// (first < rg.nrblocks, wave-uniform), as lane `lane` of wave `wv` of the
+// workgroup.  `lut` and `sq` are the workgroup's coder and squeeze tables,
+// `spos` its kWavesPerGroup * 64 positions, `lds` the slots; the wave's own
+// slots are zero on entry.  The body of encode3_region, which encode3_boxes
+// (kernels_boxes_enc.h) runs per region of a batch.
 // Lanes past the region's last block code that last block again (so that every
 // wave is whole where the coder's wave-uniform branches stage cooperatively)
 // and take no part in the copy-out.
-template <typename S, bool HI = false, int D = 3>
-__global__ __launch_bounds__(256, 1) void encode3_region(const S* __restrict__ src, Geometry g, CodecParams cp,
-                                                        RegionGeom rg, RegionEncArgs a)
+// (The structs come by value: by reference the same body took 4 to 7 VGPRs
+// more, and three instantiations of encode3_region lost a wave per SIMD.)
+template <typename S, bool HI, int D>
+__device__ __forceinline__ void region_enc_wave(const S* __restrict__ src, const Geometry g, const CodecParams cp,
+                                                const RegionGeom rg, const RegionEncArgs a, const uint64_t first,
+                                                const int lane, const int wv, const uint32_t* lut, const uint32_t* sq,
+                                                uint64_t* spos, uint64_t* lds)
 {
-  __shared__ uint32_t lut[256];
-  __shared__ uint32_t sq[256];
-  __shared__ uint64_t spos[kWavesPerGroup * 64];
-  extern __shared__ uint64_t lds[];
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
   uint64_t* wslot = lds + (size_t)wv * 64 * a.swp;
-  // every wave writes both (identical) tables and zeroes its own slots: no
-  // workgroup barrier
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    sq[lane + 64 * k] = squeeze_entry(lane + 64 * k);
-    lut[lane + 64 * k] = kCoderTables.dbl[lane + 64 * k];
-  }
-  for (uint32_t i = lane; i < 64 * a.swp; i += 64)
-    wslot[i] = 0;
-  const uint64_t first = ((uint64_t)blockIdx.x * kWavesPerGroup + wv) * 64;
-  if (first >= rg.nrblocks)  // (wave-uniform)
-    return;
   const uint64_t nb = (rg.nrblocks - first) < 64 ? (rg.nrblocks - first) : 64;
   const bool act = (uint64_t)lane < nb;
   const uint32_t q = (uint32_t)(act ? first + lane : rg.nrblocks - 1);
@@ -316,6 +306,34 @@ __global__ __launch_bounds__(256, 1) void encode3_region(const S* __restrict__ s
       (void)__hip_atomic_fetch_or(w, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+
+// HI: double with maxprec <= 32.  D: block dimensionality; 1D/2D blocks and
+// integer fields take the generic per-lane codec (blockn.h).
+template <typename S, bool HI = false, int D = 3>
+__global__ __launch_bounds__(256, 1) void encode3_region(const S* __restrict__ src, Geometry g, CodecParams cp,
+                                                        RegionGeom rg, RegionEncArgs a)
+{
+  __shared__ uint32_t lut[256];
+  __shared__ uint32_t sq[256];
+  __shared__ uint64_t spos[kWavesPerGroup * 64];
+  extern __shared__ uint64_t lds[];
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  uint64_t* wslot = lds + (size_t)wv * 64 * a.swp;
+  // every wave writes both (identical) tables and zeroes its own slots: no
+  // workgroup barrier
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    sq[lane + 64 * k] = squeeze_entry(lane + 64 * k);
+    lut[lane + 64 * k] = kCoderTables.dbl[lane + 64 * k];
+  }
+  for (uint32_t i = lane; i < 64 * a.swp; i += 64)
+    wslot[i] = 0;
+  const uint64_t first = ((uint64_t)blockIdx.x * kWavesPerGroup + wv) * 64;
+  if (first >= rg.nrblocks)  // (wave-uniform)
+    return;
+  region_enc_wave<S, HI, D>(src, g, cp, rg, a, first, lane, wv, lut, sq, spos, lds);
 }
 
 // Launcher (zfp_region_enc.hip holds every instantiation).  type: zfp_type;

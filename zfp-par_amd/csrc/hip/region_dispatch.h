@@ -1,6 +1,7 @@
 // Which instantiations of the region kernels exist: the one selection ladder
-// of the region decode, batched region decode and region encode launch units
-// (zfp_region.hip, zfp_boxes.hip, zfp_region_enc.hip).  It knows nothing about
+// of the region decode, batched region decode, region encode and batched region
+// encode launch units (zfp_region.hip, zfp_boxes.hip, zfp_region_enc.hip,
+// zfp_boxes_enc.hip).  It knows nothing about
 // the kernels: each unit passes a callable that launches its own.
 #pragma once
 

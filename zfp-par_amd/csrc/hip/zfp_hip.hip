@@ -30,6 +30,7 @@
 #include "host_region.h"       // region decode, and the host pieces every region call shares
 #include "host_region_enc.h"   // region encode: validation, source image, launch, copy-back
 #include "host_boxes.h"        // batched region decode: validation, the region table, launch, copy-out
+#include "host_boxes_enc.h"    // batched region encode: validation, disjointness, sources, launch, copy-back
 
 // ---------------------------------------------------------------------------
 // How every entry point that uses the device begins: the job's plan, the
@@ -341,6 +342,32 @@ int zfp_hip_compress_region(const zfp_hip_job* job, const uint64_t lo[4], const 
   const int ok = region_enc_once(lease.c, p, rg, src, src_stride, words, capacity_words, bit_offset);
   if (ok && blocks_written)
     *blocks_written = rg.nrblocks;
+  return lease.done(ok);
+}
+
+int zfp_hip_compress_regions(const zfp_hip_job* job, const zfp_hip_src_region* regions, uint64_t nregions,
+                             uint64_t* words, uint64_t capacity_words, uint64_t bit_offset, int device,
+                             uint64_t* blocks_written)
+{
+  const char* who = "zfp_hip_compress_regions";
+  Plan p;
+  BoxesPlan bp;
+  std::vector<BoxRecord> rec;          // (these outlive the lease: they may have to wait for their copies)
+  std::vector<std::vector<char>> tmp;  // packed rows of host sources
+  t_timing = Timing{};
+  if (!plan_regions_enc(job, regions, nregions, words, capacity_words, bit_offset, p, bp))
+    return 0;
+  if (nregions == 0) {
+    if (blocks_written)
+      *blocks_written = 0;
+    return 1;
+  }
+  CtxLease lease;
+  if (!open_call(lease, who, device))
+    return 0;
+  const int ok = regions_enc_once(lease.c, p, bp, rec, tmp, regions, words, capacity_words, bit_offset);
+  if (ok && blocks_written)
+    *blocks_written = bp.blocks;
   return lease.done(ok);
 }
 

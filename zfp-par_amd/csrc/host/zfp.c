@@ -1277,6 +1277,26 @@ zfp_bool zfp_decompress_regions(zfp_stream* zfp, const zfp_field* field, const z
   return ok;
 }
 
+/* The bits pending in the bitstream's buffer, stored into the word they belong
+ * to (s->ptr stays), after a region encode has merged into the stream. */
+static zfp_bool store_pending_bits(bitstream* s)
+{
+  if (s->bits) {
+    const uint64 m = ((uint64)1 << s->bits) - 1;
+    uint64 w = 0;
+    if (s->device) {
+      if (!zfp_hip_memcpy(&w, s->ptr, sizeof w))
+        return zfp_false;
+      w = (w & ~m) | (s->buffer & m);
+      if (!zfp_hip_memcpy(s->ptr, &w, sizeof w))
+        return zfp_false;
+    } else {
+      *s->ptr = (*s->ptr & ~m) | (s->buffer & m);
+    }
+  }
+  return zfp_true;
+}
+
 /* Region encode (no reference equivalent): the blocks of `coded` that intersect
  * `region`, coded again from `in` in place -- zfp_hip_compress_region with the
  * stream's device and its write position (stream_wtell), which stays where it
@@ -1305,21 +1325,44 @@ zfp_bool zfp_compress_region(zfp_stream* zfp, const zfp_field* field, const zfp_
     report("zfp_compress_region");
     return zfp_false;
   }
-  if (s->bits) {
-    /* the pending bits into the word they belong to (s->ptr stays) */
-    const uint64 m = ((uint64)1 << s->bits) - 1;
-    uint64 w = 0;
-    if (s->device) {
-      if (!zfp_hip_memcpy(&w, s->ptr, sizeof w))
-        return zfp_false;
-      w = (w & ~m) | (s->buffer & m);
-      if (!zfp_hip_memcpy(s->ptr, &w, sizeof w))
-        return zfp_false;
-    } else {
-      *s->ptr = (*s->ptr & ~m) | (s->buffer & m);
+  return store_pending_bits(s);
+}
+
+/* Batched region encode: every (regions[i], ins[i]) pair as
+ * zfp_compress_region, in one zfp_hip_compress_regions call.  A mismatch in
+ * any pair fails the call before anything is written. */
+zfp_bool zfp_compress_regions(zfp_stream* zfp, const zfp_field* field, const zfp_chunk* coded,
+                              const zfp_chunk* regions, size_t nregions, const zfp_field* const* ins)
+{
+  bitstream* s;
+  zfp_hip_job job;
+  zfp_hip_src_region* r;
+  zfp_bool ok = zfp_true;
+  uint d;
+  if (!zfp || !zfp->stream || !field || (nregions && (!regions || !ins)))
+    return zfp_false;
+  s = zfp->stream;
+  if (variable_rate(zfp, field))
+    return zfp_false;
+  d = zfp_field_dimensionality(field);
+  r = (zfp_hip_src_region*)malloc((nregions ? nregions : 1) * sizeof(*r));
+  if (!r)
+    return zfp_false;
+  for (size_t i = 0; ok && i < nregions; i++) {
+    ok = ins[i] && region_pair(field, d, &regions[i], ins[i], r[i].lo, r[i].hi, r[i].src_stride);
+    if (ok)
+      r[i].src = ins[i]->data;
+  }
+  if (ok) {
+    (void)region_job(&job, zfp, field, coded); /* (fixed rate: no index) */
+    if (!zfp_hip_compress_regions(&job, r, nregions, s->begin, (uint64)(s->end - s->begin), stream_wtell(s),
+                                  stream_device(zfp), NULL)) {
+      report("zfp_compress_regions");
+      ok = zfp_false;
     }
   }
-  return zfp_true;
+  free(r);
+  return ok && store_pending_bits(s);
 }
 
 /* One block of the low-level API (encode.c / decode.c templates: zfp_encode_

@@ -6,7 +6,8 @@ chunked compression of a shared array.  The codec runs in hand-written HIP
 kernels (libzfp_hip.so) behind the zfp C API (libzfp.so).
 """
 from .zfpy_c import (HEADER_FULL, HEADER_MAGIC, HEADER_META, HEADER_MODE, _decompress, compress_numpy,
-                     compress_numpy_portion, compress_region, decompress_numpy, decompress_numpy_portion,
+                     compress_numpy_portion, compress_region, compress_regions, decompress_numpy,
+                     decompress_numpy_portion,
                      decompress_region, decompress_regions,
                      device_count, dtype_to_format,
                      dtype_to_ztype, header,
@@ -16,7 +17,7 @@ from .zfpy_c import (HEADER_FULL, HEADER_MAGIC, HEADER_META, HEADER_MODE, _decom
 from ._zfp_par import zfp_p as zfp_parallel
 from ._zfp_par import read_json_header, write_json_header
 
-__all__ = ["compress_numpy", "decompress_numpy", "decompress_region", "decompress_regions", "compress_region", "zfp_parallel", "header", "zfp_chunkit", "compress_numpy_portion",
+__all__ = ["compress_numpy", "decompress_numpy", "decompress_region", "decompress_regions", "compress_region", "compress_regions", "zfp_parallel", "header", "zfp_chunkit", "compress_numpy_portion",
            "decompress_numpy_portion", "mode_expert", "mode_fixed_accuracy", "mode_fixed_precision",
            "mode_fixed_rate", "mode_null", "mode_reversible", "type_none", "type_int32", "type_int64", "type_float",
            "type_double", "HEADER_FULL", "HEADER_MAGIC", "HEADER_META", "HEADER_MODE", "_decompress",

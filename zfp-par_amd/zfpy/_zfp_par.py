@@ -21,7 +21,8 @@ from multiprocessing.sharedctypes import RawArray
 
 import numpy as np
 
-from .zfpy_c import (_compress_portion, _compress_region_bytes, _decompress_portion, _decompress_region_stream,
+from .zfpy_c import (_check_disjoint_blocks, _compress_portion, _compress_region_bytes, _compress_regions_bytes,
+                     _decompress_portion, _decompress_region_stream,
                      _decompress_regions_stream, _fixed_rate, _region_box, device_count, zfp_chunkit)
 
 _TYPECODE = {"float32": "f", "float64": "d", "int32": "i", "int64": "q"}
@@ -228,6 +229,64 @@ class zfp_p:
         def one(i, coded, part):
             view = values[tuple(slice(f - f0, e - f0) for (f, e), (f0, _) in zip(part, box))]
             return i, _compress_region_bytes(data[i], coded, part, view, self._device_of(i))
+
+        with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
+            res = pool.starmap(one, tasks)
+        for i, new in res:  # (all tasks succeeded: a failure leaves every stream as it was)
+            data[i] = new
+        return data
+
+    def compress_regions(self, regions, values=None, nthreads=-1):
+        """Code many regions again (each as for compress_region; values: a list of ndarrays, one per
+        region, or None: the shared array's own elements), with one batched native call per touched
+        chunk for that chunk's parts of all the regions, on the thread pool.  Every touched chunk gets
+        one new bytes object, the other chunks keep their stream objects, and the streams are swapped
+        only after every task succeeded.  Within one chunk no 4^d block (counted from the chunk's
+        origin) may intersect the parts of two regions: ValueError, before any chunk is touched.
+        Returns the list of chunk streams."""
+        if nthreads == -1:
+            nthreads = cpu_count()
+        data = self._compress_data
+        ck = self._chunkit
+        if len(data) != ck.get_nchunks():
+            raise RuntimeError("no compressed data for this partition (call compress first)")
+        if not self._fixed:
+            raise RuntimeError("compress_regions needs fixed-rate chunk streams (compress(rate=...)): in a "
+                               "variable-rate stream a block of another length moves every later block")
+        nd = ck.ndim
+        boxes = [_region_box(r, tuple(ck.ns_python)) for r in regions]
+        if values is None:
+            values = [self._np_array[tuple(slice(f, e) for f, e in box)] for box in boxes]
+        values = list(values)
+        if len(values) != len(boxes):
+            raise ValueError("%d value arrays for %d regions" % (len(values), len(boxes)))
+        for k, (v, box) in enumerate(zip(values, boxes)):
+            if not isinstance(v, np.ndarray):
+                raise TypeError("values[%d] must be a numpy array" % k)
+            if v.dtype != np.dtype(ck.dtype):
+                raise TypeError("values[%d] of dtype %s, the array holds %s" % (k, v.dtype, np.dtype(ck.dtype)))
+            if v.shape != tuple(e - f for f, e in box):
+                raise ValueError("values[%d] of shape %s, its region has shape %s"
+                                 % (k, v.shape, tuple(e - f for f, e in box)))
+        tasks = []
+        for i in range(len(data)):
+            coded = list(reversed(ck.boxes[i][:nd]))  # numpy axis order
+            parts, views, owner = [], [], []
+            for k, box in enumerate(boxes):
+                part = [(max(f, cf), min(e, ce)) for (f, e), (cf, ce) in zip(box, coded)]
+                if all(f < e for f, e in part):
+                    parts.append(part)
+                    views.append(values[k][tuple(slice(f - f0, e - f0) for (f, e), (f0, _) in zip(part, box))])
+                    owner.append(k)
+            if parts:
+                try:
+                    _check_disjoint_blocks(parts, coded, "parts")
+                except ValueError as err:
+                    raise ValueError("chunk %d, regions %s: %s" % (i, owner, err)) from None
+                tasks.append((i, coded, parts, views))
+
+        def one(i, coded, parts, views):
+            return i, _compress_regions_bytes(data[i], coded, parts, views, self._device_of(i))
 
         with ThreadPool(processes=max(1, min(nthreads, len(tasks) or 1))) as pool:
             res = pool.starmap(one, tasks)

@@ -63,6 +63,7 @@ for _name, _res, _args in [
     ("zfp_decompress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
     ("zfp_decompress_regions", _i32, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zfp_compress_region", _i32, [_vp, _vp, _vp, _vp, _vp]),
+    ("zfp_compress_regions", _i32, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("stream_rtell", _u64, [_vp]), ("stream_wseek", None, [_vp, _u64]),
     ("zfp_write_header", _sz, [_vp, _vp, _u32]), ("zfp_read_header", _sz, [_vp, _vp, _u32]),
     ("zfp_optimal_parts_from_size", _vp, [_i32, _vp, ctypes.c_float, _i32]),
@@ -738,6 +739,144 @@ def _compress_region_bytes(data, coded_box, box, values, device):
     out, addr = _bytes_target(n)
     ctypes.memmove(addr, _bytes_addr(data), n)
     _compress_region_at(addr, n, coded_box, box, values, device)
+    return out
+
+
+def _block_ranges(box, coded):
+    """The blocks `box` intersects, per numpy axis as (first, last), counted
+    from the origin of `coded` ([(first, end)] per axis)."""
+    return [((f - cf) // 4, (e - 1 - cf) // 4) for (f, e), (cf, _) in zip(box, coded)]
+
+
+def _shared_block_pair(ranges):
+    """ranges[i]: _block_ranges of entry i.  The numbers (i, j), i < j, of two
+    entries that share a block, or None: the native library's sweep along the
+    slowest axis with a list of the entries that still reach the current one."""
+    order = sorted(range(len(ranges)), key=lambda i: (ranges[i][0][0], i))
+    active = []
+    for e in order:
+        first = ranges[e][0][0]
+        active = [o for o in active if ranges[o][0][1] >= first]
+        for o in active:
+            if all(a0 <= b1 and b0 <= a1 for (a0, a1), (b0, b1) in zip(ranges[o], ranges[e])):
+                return min(o, e), max(o, e)
+        active.append(e)
+    return None
+
+
+def _check_disjoint_blocks(boxes, coded, what="regions"):
+    pair = _shared_block_pair([_block_ranges(b, coded) for b in boxes])
+    if pair is not None:
+        raise ValueError("%s[%d] and %s[%d] share a block: the block sets of one batch must be disjoint (merge the "
+                         "regions or make two calls)" % (what, pair[0], what, pair[1]))
+
+
+def _compress_regions_at(addr, nbytes, coded_box, boxes, values, device):
+    """zfp_compress_regions on the stream with a full header in the `nbytes`
+    writable bytes at `addr` (a whole number of 64-bit words), in place, with
+    one native call.  coded_box: as _compress_region_at; boxes: a list of
+    [(first, end)] per numpy axis, or a function of the stream's shape that
+    returns it; values[i]: ndarray of box i's shape and the stream's dtype.
+    Returns the number of blocks coded."""
+    field = _lib.zfp_field_alloc()
+    bstream = _lib.stream_open(addr, nbytes)
+    stream = _lib.zfp_stream_open(bstream)
+    try:
+        if device >= 0:
+            _lib.zfp_stream_set_hip_device(stream, device)
+        if _lib.zfp_read_header(stream, field, HEADER_FULL) == 0:
+            raise ValueError("Failed to read required zfp header")
+        fld = ctypes.cast(field, ctypes.POINTER(_Field)).contents
+        shape = tuple(n for n in (fld.nw, fld.nz, fld.ny, fld.nx) if n > 0)
+        mb, xb, mp, me = _u32(), _u32(), _u32(), _i32()
+        _lib.zfp_stream_params(stream, ctypes.byref(mb), ctypes.byref(xb), ctypes.byref(mp), ctypes.byref(me))
+        if mb.value != xb.value or me.value < _ZFP_MIN_EXP:
+            raise ValueError("compress_regions needs a fixed-rate stream (in a variable-rate stream a block of "
+                             "another length moves every later block)")
+        if callable(boxes):
+            boxes = boxes(shape)
+        values = list(values)
+        if len(values) != len(boxes):
+            raise ValueError("%d value arrays for %d regions" % (len(values), len(boxes)))
+        dtype = np.dtype(ztype_to_dtype(fld.type))
+        for i, (v, box) in enumerate(zip(values, boxes)):
+            if not isinstance(v, np.ndarray):
+                raise TypeError("values[%d] must be a numpy array" % i)
+            if v.dtype != dtype:
+                raise TypeError("values[%d] of dtype %s, the stream holds %s" % (i, v.dtype, dtype))
+            want = tuple(e - f for f, e in box)
+            if v.shape != want:
+                raise ValueError("values[%d] of shape %s, its region has shape %s" % (i, v.shape, want))
+        coded = coded_box if coded_box is not None else [(0, n) for n in shape]
+        _check_disjoint_blocks(boxes, coded)
+        nblocks = 0
+        for box in boxes:
+            k = 1
+            for b0, b1 in _block_ranges(box, coded):
+                k *= b1 - b0 + 1
+            nblocks += k
+        n = len(boxes)
+        if n == 0:
+            return 0
+        # the header was read: the same position, for writing
+        _lib.stream_wseek(bstream, _lib.stream_rtell(bstream))
+        cck = _chunk_of(list(reversed(coded_box))) if coded_box is not None else None
+        cks = (_Chunk * n)()
+        ifields = (_vp * n)()
+        try:
+            for i, (box, v) in enumerate(zip(boxes, values)):
+                for (f, e), ax in zip(reversed(box), "xyzw"):
+                    setattr(cks[i], "f" + ax, f)
+                    setattr(cks[i], "e" + ax, e)
+                ifields[i] = _make_field(v.ctypes.data, fld.type, list(reversed(v.shape)),
+                                         [s // v.itemsize for s in reversed(v.strides)])
+            ret = _lib.zfp_compress_regions(stream, field, ctypes.byref(cck) if cck is not None else None, cks, n,
+                                            ifields)
+        finally:
+            for f in ifields:
+                if f:
+                    _lib.zfp_field_free(f)
+        if not ret:
+            raise RuntimeError("error during zfp batched region compression")
+        return nblocks
+    finally:
+        _lib.zfp_field_free(field)
+        _lib.zfp_stream_close(stream)
+        _lib.stream_close(bstream)
+
+
+def compress_regions(stream, regions, values, *, device=-1):
+    """Rewrite many regions of the array that a fixed-rate stream with a full
+    header codes, in place, with one native call and one GPU launch: what one
+    compress_region(stream, regions[i], values[i]) per entry leaves, in any
+    order.  stream: as for compress_region (a read-only buffer raises
+    TypeError, a variable-rate stream ValueError).  regions: a list as for
+    decompress_regions.  values: a list of ndarrays, values[i] of region i's
+    shape and the stream's dtype with any strides; an (N, d, h, w) array gives
+    its rows.  No 4^d block may intersect two regions (their elements being
+    disjoint is not enough): ValueError, with the stream untouched.  Returns
+    the total number of blocks rewritten.  1D to 3D arrays."""
+    if stream is None:
+        raise TypeError("stream cannot be None")
+    mv = memoryview(stream)
+    if mv.readonly:
+        raise TypeError("compress_regions updates the stream in place: it needs a writable buffer "
+                        "(bytearray, writable memoryview or uint8 ndarray), not %s" % type(stream).__name__)
+    buf = np.frombuffer(mv, dtype=np.uint8)
+    if buf.size == 0 or buf.size % 8:
+        raise ValueError("stream of %d bytes is not a whole number of 64-bit words" % buf.size)
+    regions = list(regions)
+    return _compress_regions_at(buf.ctypes.data, buf.size, None,
+                                lambda shape: [_region_box(r, shape) for r in regions], list(values), device)
+
+
+def _compress_regions_bytes(data, coded_box, boxes, values, device):
+    """A new bytes object: the chunk stream `data` (bytes) with `boxes`
+    rewritten from `values` in one call (as _compress_region_bytes)."""
+    n = len(data)
+    out, addr = _bytes_target(n)
+    ctypes.memmove(addr, _bytes_addr(data), n)
+    _compress_regions_at(addr, n, coded_box, boxes, values, device)
     return out
 
 
